@@ -5,7 +5,8 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path (phmm_batch_launch: the forward kernels, nothing else) over one batch of
-synthetic assembly regions already resident in HBM.
+synthetic assembly regions already resident in HBM.  `--dump-outputs DIR` writes the likelihoods of the last timed step to
+DIR/*.npy (dump_outputs()); the inputs depend on the arguments alone, so two builds can be compared output for output.
 
 `value` (every N): per GPU `--regions` (default 1024) regions of the BASELINE.json configs[1] shape -- 128 reads x 8
 haplotypes, 150 bp reads, 300 bp haplotypes -- i.e. SURVEY.md 8(d)'s batched form of config 2; rank r draws its own
@@ -76,7 +77,13 @@ def parse():
                          "survives in L2 / Infinity Cache from the previous launch (the timing then includes the fill)")
     ap.add_argument("--main-only", action="store_true",
                     help="only the timed loop (no extra rows, no cpu_baseline): for PMC passes")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop's last step computed (the likelihoods, float64) to DIR/*.npy, so that two "
+                         "builds can be compared output for output; see dump_outputs()")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def make_workload(name, n_regions, seed):
@@ -381,6 +388,27 @@ def strong_row(D, eng, stream, name, steps, sample):
     return row
 
 
+DUMP_MAX_BYTES = 60 * 10**6  # what --dump-outputs may write in all: under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, likelihoods, rank, world):
+    """DIR/likelihoods.npy: the float64 log10 likelihoods of the timed launch's last step, one per (read, haplotype) pair in
+    the batch's out_off order -- what a caller of phmm_batch_launch receives.  Past DUMP_MAX_BYTES a fixed sample of pairs
+    is written instead (a seeded draw that depends only on the number of pairs, kept in order) with the pairs' indices beside
+    it as DIR/likelihoods_index.npy (float64, exact).  With N > 1 ranks every rank writes its own batch's under _rank<r>,
+    within an N-th of the budget."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    n, budget = likelihoods.size, DUMP_MAX_BYTES // world
+    if n * 8 > budget:
+        keep = budget // 16  # (the values and their indices, 8 bytes each)
+        idx = np.sort(np.random.Generator(np.random.Philox(np.random.SeedSequence([20251015, n]))).choice(n, keep, replace=False))
+        np.save(os.path.join(out_dir, "likelihoods%s_index.npy" % suffix), idx.astype(np.float64))
+        likelihoods = likelihoods[idx]
+    np.save(os.path.join(out_dir, "likelihoods%s.npy" % suffix), np.ascontiguousarray(likelihoods, dtype=np.float64))
+
+
 def write_full_record(line):
     """Everything the run measured, with its explanatory notes, as a file (stdout carries the compact line below)."""
     out_dir = os.path.join(ROOT, "gpurun_out") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else os.environ.get("TMPDIR", "/tmp")
@@ -531,6 +559,8 @@ def main():
 
     flush = torch.empty(1 << 28, dtype=torch.float32, device=dev) if a.flush_caches else None
     elapsed, kern_ms = timed_launches(D, res, stream, a.steps, a.warmup, flush)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out.cpu().numpy(), rank, world)
     cells_total = plan.cells * world  # identical shapes on every rank
     regions_total = regions * world
     per_rank_cells = [int(c) for c in D.gather(plan.cells)]  # (every rank takes part)

@@ -8,9 +8,10 @@ No Rust toolchain exists in this image, so the A/B run of `lorikeet call` itself
 the patches apply to the reference tree, the Rust declarations agree with the C header name by name (arity, pointer
 depth, constness, scalar width), and a plain C99 translation unit that calls every export compiles against the
 header and links against the library."""
+import hashlib
+import json
 import os
 import re
-import shutil
 import subprocess
 import tempfile
 
@@ -21,7 +22,6 @@ HEADER = os.path.join(ROOT, "include", "phmm.h")
 FFI = os.path.join(ROOT, "integration", "hip_ffi.rs")
 PATCH = os.path.join(ROOT, "integration", "lorikeet-hip.patch")
 PATCH2 = os.path.join(ROOT, "integration", "lorikeet-hip-shared-handle.patch")
-REFERENCE = "/root/reference"
 
 C_SCALARS = {"int": "i32", "unsigned": "u32", "unsigned int": "u32", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64",
              "int32_t": "i32", "int64_t": "i64", "double": "f64", "size_t": "usize", "char": "c_char", "void": "void",
@@ -207,12 +207,33 @@ def test_the_safe_wrapper_calls_what_the_ffi_declares():
         assert backend.count(o) == backend.count(c), (o, c)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference tree only exists in the build container")
+def _pre_images(patch_text):
+    """{file: [(start, count, pre-image lines)]} of every hunk: its context and '-' lines, at the old file's lines it names"""
+    out, cur, h = {}, None, None
+    for ln in patch_text.splitlines():
+        if ln.startswith("diff --git"):
+            cur, h = ln.split(" b/")[1], None
+            continue
+        m = re.match(r"^@@ -(\d+)(?:,(\d+))? \+\d+(?:,\d+)? @@", ln)
+        if m:
+            h = (int(m.group(1)), 1 if m.group(2) is None else int(m.group(2)), [])
+            out.setdefault(cur, []).append(h)
+        elif h is not None and ln[:1] in (" ", "-"):
+            h[2].append(ln[1:])
+    return out
+
+
 def test_patches_apply_to_the_reference_tree():
-    r = subprocess.run(["git", "apply", "--check", "--verbose", PATCH], cwd=REFERENCE, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    """The patch's hunks are checked against what tests/golden/reference_tree_facts.json stores of the reference tree (the
+    SHA-256 of its lines under every hunk, its line counts, which files exist): a hunk whose pre-image hashes to the stored
+    value applies at the very line it names, which is what `git apply --check` verifies on the tree.  The second patch is
+    then applied on top of the first, for real, on files that hold the reference's lines under the hunks (all the first
+    patch needs) and blank lines elsewhere."""
+    facts = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_tree_facts.json")))["patch_base"]
+    text = open(PATCH).read()
+    pre = _pre_images(text)
     # the files the reviews name (pair_hmm.rs:345-375, ...engine.rs:654-672, cli.rs:1928/2706/3485, assembly_based_caller_utils.rs:960-964)
-    touched = set(re.findall(r"^diff --git a/(\S+)", open(PATCH).read(), flags=re.M))
+    touched = set(re.findall(r"^diff --git a/(\S+)", text, flags=re.M))
     assert {"src/pair_hmm/pair_hmm.rs", "src/pair_hmm/pair_hmm_likelihood_calculation_engine.rs", "src/cli.rs",
             "src/assembly/assembly_based_caller_utils.rs", "src/smith_waterman/smith_waterman_aligner.rs",
             "src/pair_hmm/hip_ffi.rs", "src/pair_hmm/hip_backend.rs", "src/pair_hmm/mod.rs", "build.rs", "Cargo.toml",
@@ -221,22 +242,29 @@ def test_patches_apply_to_the_reference_tree():
             # haplotype_caller_engine.rs:1345-1355, create_read_aligned_to_ref's tail, calculate_cigar cigar_utils.rs:358-457)
             "src/haplotype/haplotype_caller_engine.rs", "src/model/allele_likelihoods.rs", "src/reads/alignment_utils.rs",
             "src/reads/cigar_utils.rs"} <= touched
-    assert open(PATCH).read().count('Arg::new("pairhmm-backend")') == 3   # one per subcommand that has --disable-avx
-    # second patch: on a copy of the touched files with the first one applied
+    assert text.count('Arg::new("pairhmm-backend")') == 3   # one per subcommand that has --disable-avx
+    assert set(facts) == touched, "tests/golden/reference_tree_facts.json is not of this patch: rebuild it"
+    for f in sorted(touched):
+        if not facts[f]["exists"]:  # a file the patch creates
+            assert [h[:2] for h in pre[f]] == [(0, 0)], f
+            continue
+        stored = facts[f]["hunks"]
+        assert sorted(stored) == sorted("%d,%d" % h[:2] for h in pre[f]), "%s: the hunks moved: rebuild the facts" % f
+        for start, count, lines in pre[f]:
+            assert len(lines) == count and start - 1 + count <= facts[f]["lines"], (f, start, count)
+            got = hashlib.sha256("".join(ln + "\n" for ln in lines).encode()).hexdigest()
+            assert got == stored["%d,%d" % (start, count)], "%s @@ -%d,%d: the pre-image is not the reference's" % (f, start, count)
     with tempfile.TemporaryDirectory() as d:
         for f in touched:
-            src = os.path.join(REFERENCE, f)
-            if os.path.exists(src):
+            if facts[f]["exists"]:
+                body = [""] * facts[f]["lines"]
+                for start, count, lines in pre[f]:
+                    body[start - 1:start - 1 + count] = lines
                 os.makedirs(os.path.dirname(os.path.join(d, f)), exist_ok=True)
-                shutil.copy(src, os.path.join(d, f))
+                open(os.path.join(d, f), "w").write("\n".join(body) + "\n")
         subprocess.run(["git", "init", "-q", "."], cwd=d, check=True)
-        r = subprocess.run(["git", "apply", PATCH], cwd=d, capture_output=True, text=True)
+        r = subprocess.run(["git", "apply", "--check", "--verbose", PATCH], cwd=d, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
-        r = subprocess.run(["git", "apply", "--check", PATCH2], cwd=d, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        r = subprocess.run(["git", "apply", PATCH2], cwd=d, capture_output=True, text=True)
-        backend = open(os.path.join(d, "src/pair_hmm/hip_backend.rs")).read()
-        assert "phmm_submit(" in backend and "phmm_wait(h, ticket)" in backend and "phmm_compute(" not in backend
         # the patches add balanced delimiters to every Rust file they produce or touch (the cheapest syntax check there
         # is without rustc): open-minus-close of each bracket kind is what it was before (0 for new files)
         def surplus(path):
@@ -246,9 +274,16 @@ def test_patches_apply_to_the_reference_tree():
             text = re.sub(r'"(?:\\.|[^"\\])*"', '""', text)
             text = re.sub(r"'(?:\\.|[^'\\])'", "''", text)
             return tuple(text.count(o) - text.count(c) for o, c in ("()", "[]", "{}"))
-        for f in touched:
-            if f.endswith(".rs"):
-                assert surplus(os.path.join(d, f)) == surplus(os.path.join(REFERENCE, f)), f
+        before = {f: surplus(os.path.join(d, f)) for f in touched if f.endswith(".rs")}
+        r = subprocess.run(["git", "apply", PATCH], cwd=d, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        r = subprocess.run(["git", "apply", "--check", PATCH2], cwd=d, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        r = subprocess.run(["git", "apply", PATCH2], cwd=d, capture_output=True, text=True)
+        backend = open(os.path.join(d, "src/pair_hmm/hip_backend.rs")).read()
+        assert "phmm_submit(" in backend and "phmm_wait(h, ticket)" in backend and "phmm_compute(" not in backend
+        for f, was in before.items():
+            assert surplus(os.path.join(d, f)) == was, f
 
 
 def test_the_patch_binds_every_call_site_of_the_path():

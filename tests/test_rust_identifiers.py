@@ -9,19 +9,16 @@ from the reference tree is resolved here against that tree with a small tokenize
 * every other called name is one of ours (defined in the added code, a local closure / binding), or belongs to the short,
   reviewed lists below (std, rust-htslib's bam::Record and Cigar, clap, rayon) -- an unknown name fails;
 * field accesses resolve to a field of a reference struct or of ours.
-Runs in the build container only (needs /root/reference)."""
-import glob
+The reference's side of the index is stored data (tests/golden/reference_tree_facts.json, built from the reference tree by
+tests/golden/make_reference_tree_facts.py): the suite does not need the tree itself."""
+import json
 import os
 import re
 
-import pytest
-
 import rust_index as R
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
-REFERENCE = "/root/reference"
 PATCH = os.path.join(ROOT, "integration", "lorikeet-hip.patch")
-pytestmark = pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference tree only exists in the build container")
 
 STD = set("""and_then any as_mut_ptr as_ptr as_ref as_slice as_str borrow_mut by_ref cloned collect entry enumerate expect
 extend_from_slice fetch_and fetch_or flat_map flatten for_each from_ptr get_mut insert into_iter into_owned is_none iter iter_mut keys
@@ -36,20 +33,10 @@ EXTERNAL = STD | HTSLIB | CLAP | RAYON
 
 
 def _reference_index():
-    fns, items, fields, variants, impls = {}, set(), set(), set(), {}
-    for f in glob.glob(os.path.join(REFERENCE, "src", "**", "*.rs"), recursive=True):
-        t = R.strip(open(f).read())
-        d = R.definitions(t)
-        for k, v in d[0].items():
-            fns.setdefault(k, set()).update(v)
-        items |= d[1]
-        fields |= d[2]
-        variants |= d[3]
-        for m in re.finditer(r"\bimpl\b\s*(?:<[^{]*?>\s*)?(?:[A-Za-z_][\w:]*(?:<[^{]*?>)?\s+for\s+)?([A-Za-z_]\w*)[^{;]*\{", t):
-            end = R._match(t, m.end() - 1, "{", "}")
-            for k, v in R.definitions(t[m.end():end - 1])[0].items():
-                impls.setdefault(m.group(1), {}).setdefault(k, set()).update(v)
-    return fns, items, fields, variants, impls
+    """(sizes of the whole index, fns, items, fields, variants, impls) of the reference's src/**/*.rs, as stored"""
+    d = json.load(open(os.path.join(GOLDEN, "reference_tree_facts.json")))["rust_index"]
+    return (d["sizes"], {k: set(v) for k, v in d["fns"].items()}, set(d["items"]), set(d["fields"]), set(d["variants"]),
+            {t: {k: set(v) for k, v in m.items()} for t, m in d["impls"].items()})
 
 
 def _our_code():
@@ -74,8 +61,8 @@ def test_the_tokenizer_on_rust_it_must_get_right():
 
 
 def test_every_name_the_rust_side_takes_from_the_reference_exists_there_with_that_arity():
-    ref_fns, ref_items, ref_fields, ref_variants, ref_impls = _reference_index()
-    assert len(ref_fns) > 1000 and "compute_read_likelihoods" in ref_fns and "AlleleLikelihoods" in ref_impls
+    ref_sizes, ref_fns, ref_items, ref_fields, ref_variants, ref_impls = _reference_index()
+    assert ref_sizes["fns"] > 1000 and "compute_read_likelihoods" in ref_fns and "AlleleLikelihoods" in ref_impls
     ours = _our_code()
     assert {"src/pair_hmm/hip_backend.rs", "src/pair_hmm/hip_ffi.rs", "src/bin/lorikeet.rs"} <= set(ours)
     text = "\n".join(ours.values())
