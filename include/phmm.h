@@ -541,6 +541,51 @@ int phmm_calculate_cigar(phmm_handle *h, uint32_t n, const uint32_t *ref_off, co
                          const uint64_t *cigar_off, uint32_t *cigar, uint32_t *n_cigar, int32_t *status);
 
 /*
+ * Per-event genotype likelihoods: the last arithmetic step of the reference's call_region,
+ * genotyping_engine.assign_genotype_likelihoods (src/haplotype/haplotype_caller_engine.rs:1379), for many regions in ONE
+ * call, on the likelihood matrices phmm_engine_compute / phmm_region_compute return.  For every event e and sample s:
+ *   reads used      the reads of e's region with read_sample == s, keep != 0, and Locatable::overlaps with the event window
+ *                   as self (src/utils/simple_interval.rs:298-307, all three clauses incl. CoordMath::encloses) -- the
+ *                   genotyping predicate of retain_evidence (haplotype_caller_genotyping_engine.rs:759-768), in region order
+ *   marginal        M[a][r] = max over haplotypes h with map[h] == a of L[r][h], from -inf (AlleleLikelihoods::marginalize,
+ *                   src/model/allele_likelihoods.rs:633-740): an allele no haplotype maps to stays -inf
+ *   genotypes       the reference's canonical index order (build_allele_first_genotype_offset_table, allele_heap_to_index:
+ *                   genotype_likelihood_calculators.rs:180-224, genotype_likelihood_calculator.rs:273-295); diploid
+ *                   0/0, 0/1, 1/1, 0/2, 1/2, 2/2, ...; G_e = phmm_genotype_count(ploidy, A_e) <= 1 024 (the reference's
+ *                   max_genotype_count_to_enumerate, haplotype_caller_genotyping_engine.rs:66)
+ *   GL              GenotypeLikelihoodCalculator::genotype_likelihoods (genotype_likelihood_calculator.rs:308-580): per read the
+ *                   one- / two- / many-component term with the JacobianLogTable sums (src/utils/math_utils.rs:314-370),
+ *                   summed over the used reads in order from 0.0, minus n_used * log10(ploidy)
+ *   PL              min(round(-10 (GL - max GL)), i32::MAX) with Rust's `as i32` (NaN -> 0): all GLs -inf gives PLs 0
+ *                   (Genotype::build_from_likelihoods, src/genotype/genotype_builder.rs:135-152, genotype_likelihoods.rs:55-78)
+ * Bit-equal to the reference's operations: no contraction, log10(k) made on the host with std::log10, the host's Jacobian
+ * table resident on the device.  Priors, the AF calculation, allele trimming and VCF output stay with the caller.
+ *   region_read_off / region_hap_off [n_regions+1], out_off [n_regions+1], likelihoods   as phmm_realign_reads
+ *   keep [n_reads] or NULL (every read kept)   0: removed by filter_poorly_modeled_evidence (phmm_engine_compute's keep)
+ *   read_sample [n_reads]   in [0, n_samples)
+ *   read_start / read_end [n_reads]   the read's closed span on the reference after realignment (get_start / get_end,
+ *                      src/reads/bird_tool_reads.rs:239-249: end = start + max(reference length - 1, 0))
+ *   ploidy             --ploidy (default 2, src/cli.rs:1934-1937), 1..65535
+ *   event_region [n_events]; event_allele_off [n_events+1] prefix sums: A_e = off[e+1] - off[e] alleles, allele 0 the reference
+ *   event_start / event_end [n_events]   the closed window, already widened by --allele-informative-reads-overlap-margin
+ *                      (default 2, haplotype_caller_genotyping_engine.rs:217-229)
+ *   event_hap_allele   per event in order, Nh(region(e)) entries: the haplotype's allele, -1 = none
+ *   gl_off [n_events+1]   event e writes n_samples x G_e doubles, sample-major [s][g], at gl + gl_off[e]; pl (or NULL) alike
+ *   n_evidence [n_events * n_samples] or NULL   the reads used
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offending event or read): a required array NULL,
+ * offsets not monotonic, ploidy 0, G_e > 1 024, A_e == 0, a map entry < -1 or >= A_e, event_region >= n_regions,
+ * read_sample >= n_samples, a gl_off slot smaller than n_samples x G_e.  n_events == 0 returns PHMM_OK.  One thread per handle.
+ */
+uint32_t phmm_genotype_count(uint32_t ploidy, uint32_t n_alleles);  /* host only; 0 if either is 0; saturates at UINT32_MAX */
+int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t *region_read_off,
+                              const uint32_t *region_hap_off, const uint64_t *out_off, const double *likelihoods,
+                              const uint8_t *keep, const uint32_t *read_sample, const int64_t *read_start,
+                              const int64_t *read_end, uint32_t n_samples, uint32_t ploidy, uint32_t n_events,
+                              const uint32_t *event_region, const uint32_t *event_allele_off, const int64_t *event_start,
+                              const int64_t *event_end, const int32_t *event_hap_allele, const uint64_t *gl_off, double *gl,
+                              int32_t *pl, uint32_t *n_evidence);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):
@@ -573,7 +618,7 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name);
  * the server to leave the chip first.  tools/server_trace.cpp prints a call's timeline from it. */
 uint32_t phmm_server_trace(int device_id, void *out, uint32_t cap);
 
-/* What the library was built from: "cigar=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
+/* What the library was built from: "cigar=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
  * family (tools/source_hash.py) at compile time.  smoke() and bench.py compare it with the tree they run in. */
 const char *phmm_build_info(void);
 
@@ -581,6 +626,9 @@ const char *phmm_build_info(void);
  * eps[q] = 10^(-q/10) for q in 0..=255, mm = triangular match->match table incl. row 255. */
 size_t phmm_table_eps(const double **eps);
 size_t phmm_table_match_to_match(const double **mm);
+/* JacobianLogTable (src/utils/math_utils.rs:9-14, :481-498): log10(1 + 10^(-k * 1e-4)) for k in 0..=80 000, the table
+ * phmm_genotype_likelihoods uses on the device */
+size_t phmm_table_jacobian(const double **table);
 
 #ifdef __cplusplus
 }

@@ -551,13 +551,42 @@ extern "C" {
         status: *mut i32,
     ) -> c_int;
 
+    /// genotyping_engine.assign_genotype_likelihoods per event (haplotype_caller_engine.rs:1379): marginalized likelihoods,
+    /// the overlapping reads of each sample, GLs and PLs for every genotype in the reference's index order
+    pub fn phmm_genotype_count(ploidy: u32, n_alleles: u32) -> u32;
+    pub fn phmm_genotype_likelihoods(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_read_off: *const u32,
+        region_hap_off: *const u32,
+        out_off: *const u64,
+        likelihoods: *const f64,
+        keep: *const u8,
+        read_sample: *const u32,
+        read_start: *const i64,
+        read_end: *const i64,
+        n_samples: u32,
+        ploidy: u32,
+        n_events: u32,
+        event_region: *const u32,
+        event_allele_off: *const u32,
+        event_start: *const i64,
+        event_end: *const i64,
+        event_hap_allele: *const i32,
+        gl_off: *const u64,
+        gl: *mut f64,
+        pl: *mut i32,
+        n_evidence: *mut u32,
+    ) -> c_int;
+
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "cigar=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "cigar=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;
     pub fn phmm_table_match_to_match(mm: *mut *const f64) -> usize;
+    pub fn phmm_table_jacobian(table: *mut *const f64) -> usize;
 }

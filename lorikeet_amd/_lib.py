@@ -118,12 +118,17 @@ SYMBOLS = [
     ("phmm_region_submit", C.c_int, _REGION_ARGS + [C.POINTER(C.c_uint64)]),
     ("phmm_region_compute_multi", C.c_int, [C.POINTER(C.c_void_p), C.c_uint32] + _REGION_ARGS[1:]),
     ("phmm_calculate_cigar", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u8p, C.c_void_p, C.c_int, u64p, u32p, u32p, C.POINTER(C.c_int32)]),
+    ("phmm_genotype_count", C.c_uint32, [C.c_uint32, C.c_uint32]),
+    ("phmm_genotype_likelihoods", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u64p, f64p, u8p, u32p, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32), u64p, f64p, C.POINTER(C.c_int32), u32p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),
     ("phmm_server_trace", C.c_uint32, [C.c_int, C.c_void_p, C.c_uint32]),
     ("phmm_table_eps", C.c_size_t, [C.POINTER(f64p)]),
     ("phmm_table_match_to_match", C.c_size_t, [C.POINTER(f64p)]),
+    ("phmm_table_jacobian", C.c_size_t, [C.POINTER(f64p)]),
 ]
 
 _lib = None

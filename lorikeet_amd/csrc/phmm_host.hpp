@@ -10,6 +10,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 // Grow-only device arena with a pinned host mirror at identical offsets.  phmm_compute() places the
@@ -123,6 +124,13 @@ struct phmm_handle {
         bool region_sw_pending = false;       // a chunk's alignment kernels wait for those of the chunk before it
         std::unordered_map<uint64_t, int> blocks_per_cu;  // by (lanes, columns, LDS bytes): asked of the runtime once
     } swork;
+    struct GtWork {  // phmm_genotype_likelihoods (phmm_genotype.cpp): grow-only staging, the resident Jacobian table
+        char *dev = nullptr, *host = nullptr;
+        size_t cap = 0;
+        double *d_jacobian = nullptr;  // JacobianLogTable, uploaded by the handle's first call
+        // the genotypes of (ploidy, alleles) in index order, by (ploidy << 32 | alleles): [G + 1] offsets, (allele | count << 16)
+        std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
+    } gwork;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

@@ -72,6 +72,7 @@ const Tables &tables() {
 
 }  // namespace
 
+const std::vector<double> &table_jacobian() { return tables().jacobian; }
 const std::vector<double> &table_eps() { return tables().eps; }
 const std::vector<double> &table_eps_third() { return tables().eps_third; }
 const std::vector<double> &table_match_to_match() { return tables().mm; }

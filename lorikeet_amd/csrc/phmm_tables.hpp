@@ -4,6 +4,7 @@
 
 namespace phmm {
 const std::vector<double> &table_eps();             // [256] 10^(-q/10)
+const std::vector<double> &table_jacobian();        // [80001] JacobianLogTable: log10(1 + 10^(-k*1e-4))
 const std::vector<double> &table_eps_third();       // [256] eps/3
 const std::vector<double> &table_match_to_match();  // [256*257/2] triangular
 double initial_condition();                         // 2^1020

@@ -1,0 +1,106 @@
+"""Per-event genotype likelihoods over the C ABI (phmm_genotype_likelihoods, include/phmm.h): the last arithmetic step of the
+reference's call_region, genotyping_engine.assign_genotype_likelihoods (src/haplotype/haplotype_caller_engine.rs:1379) --
+marginalization of the likelihood matrix to each event's alleles, the reads of each sample that overlap the event window,
+and GenotypeLikelihoodCalculator::genotype_likelihoods (src/genotype/genotype_likelihood_calculator.rs:308-580) with the
+PLs of Genotype::build_from_likelihoods.  Everything runs on the MI355X; this file only moves pointers."""
+import ctypes as C
+import itertools
+
+import numpy as np
+
+from . import _lib
+from .engine import PhmmError
+
+ALLELE_INFORMATIVE_READS_OVERLAP_MARGIN = 2  # --allele-informative-reads-overlap-margin (haplotype_caller_genotyping_engine.rs:217-229)
+MAX_GENOTYPE_COUNT = 1024  # max_genotype_count_to_enumerate (haplotype_caller_genotyping_engine.rs:66)
+_REFERENCE_OPS = (0, 2, 3, 7, 8)  # M, D, N, =, X: what CigarUtils::get_reference_length counts (src/reads/cigar_utils.rs:608-623)
+_i32p = C.POINTER(C.c_int32)
+_i64p = C.POINTER(C.c_int64)
+
+
+def _p(a, t):
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def genotype_count(ploidy, n_alleles):
+    """Genotypes of `ploidy` over `n_alleles` alleles (phmm_genotype_count: saturates at 2^32 - 1)."""
+    return int(_lib.load().phmm_genotype_count(int(ploidy), int(n_alleles)))
+
+
+def genotype_allele_counts(ploidy, n_alleles):
+    """Every genotype in the reference's index order, as its distinct alleles ascending with their counts:
+    [((allele, count), ...), ...] -- diploid over 3 alleles: 0/0, 0/1, 1/1, 0/2, 1/2, 2/2.  The index of the sorted alleles
+    a_1 <= ... <= a_p is sum offset[i][a_i] (build_allele_first_genotype_offset_table, allele_heap_to_index)."""
+    g = genotype_count(ploidy, n_alleles)
+    if g > MAX_GENOTYPE_COUNT:
+        raise ValueError("%d genotypes: more than %d" % (g, MAX_GENOTYPE_COUNT))
+    off = np.zeros((ploidy + 1, n_alleles + 1), np.int64)
+    off[0, 1:] = 1
+    for p in range(1, ploidy + 1):
+        for a in range(1, n_alleles + 1):
+            off[p, a] = off[p, a - 1] + off[p - 1, a]
+    out = [None] * g
+    for alleles in itertools.combinations_with_replacement(range(n_alleles), ploidy):
+        counts = np.bincount(np.asarray(alleles, np.int64), minlength=n_alleles)
+        out[sum(int(off[i + 1, x]) for i, x in enumerate(alleles))] = tuple((b, int(c)) for b, c in enumerate(counts) if c)
+    return out
+
+
+def read_end(new_pos, cigar):
+    """BirdToolRead::get_end (src/reads/bird_tool_reads.rs:239-249): start + max(reference length - 1, 0) for BAM-encoded
+    CIGAR elements ((length << 4) | op)."""
+    c = np.asarray(cigar, np.uint32)
+    ref_len = int(sum(int(e >> 4) for e in c if int(e & 15) in _REFERENCE_OPS))
+    return int(new_pos) + max(ref_len - 1, 0)
+
+
+class Events:
+    """The variant events of a batch: region, alleles (allele_off prefix sums), closed window, haplotype -> allele map
+    (one entry per haplotype of the event's region, concatenated in event order; -1 = none)."""
+
+    def __init__(self, region, allele_off, start, end, hap_allele):
+        self.region = np.ascontiguousarray(region, np.uint32)
+        self.allele_off = np.ascontiguousarray(allele_off, np.uint32)
+        self.start = np.ascontiguousarray(start, np.int64)
+        self.end = np.ascontiguousarray(end, np.int64)
+        self.hap_allele = np.ascontiguousarray(hap_allele, np.int32)
+
+    @property
+    def n_events(self):
+        return len(self.region)
+
+    def n_alleles(self, e):
+        return int(self.allele_off[e + 1]) - int(self.allele_off[e])
+
+
+class GenotypeResult:
+    """Per event e: gl[e] / pl[e] as [n_samples, G_e] arrays (genotypes in index order), n_evidence[e] per sample."""
+
+    def __init__(self, gl, pl, n_evidence):
+        self.gl, self.pl, self.n_evidence = gl, pl, n_evidence
+
+
+def genotype_likelihoods(engine, batch, likelihoods, keep, read_start, read_end_, read_sample, events, ploidy=2, n_samples=1):
+    """`likelihoods`: the per-region [read][hap] matrices at batch.out_off (phmm_engine_compute / phmm_region_compute);
+    `keep`: their evidence flags (or None: every read); read_start / read_end_: each read's closed span on the reference
+    after realignment (read_end); read_sample: each read's sample; events: Events."""
+    lk = np.ascontiguousarray(likelihoods, np.float64)
+    kp = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    rs, re_ = np.ascontiguousarray(read_start, np.int64), np.ascontiguousarray(read_end_, np.int64)
+    smp = np.ascontiguousarray(read_sample, np.uint32)
+    n_ev = events.n_events
+    G = np.array([genotype_count(ploidy, events.n_alleles(e)) for e in range(n_ev)], np.uint64)
+    gl_off = np.concatenate([[0], np.cumsum(G * np.uint64(n_samples))]).astype(np.uint64)
+    gl, pl = np.zeros(int(gl_off[-1])), np.zeros(int(gl_off[-1]), np.int32)
+    n_evidence = np.zeros(n_ev * n_samples, np.uint32)
+    code = engine.lib.phmm_genotype_likelihoods(
+        engine._h, batch.n_regions, _p(batch.region_read_off, _lib.u32p), _p(batch.region_hap_off, _lib.u32p), _p(batch.out_off, _lib.u64p),
+        _p(lk, _lib.f64p), _p(kp, _lib.u8p), _p(smp, _lib.u32p), _p(rs, _i64p), _p(re_, _i64p), int(n_samples), int(ploidy), n_ev,
+        _p(events.region, _lib.u32p), _p(events.allele_off, _lib.u32p), _p(events.start, _i64p), _p(events.end, _i64p),
+        _p(events.hap_allele, _i32p), _p(gl_off, _lib.u64p), _p(gl, _lib.f64p), _p(pl, _i32p), _p(n_evidence, _lib.u32p))
+    if code != _lib.PHMM_OK:
+        raise PhmmError(code, engine.last_error())
+    shape = lambda e: (int(n_samples), int(G[e]))  # noqa: E731
+    return GenotypeResult([gl[int(gl_off[e]):int(gl_off[e + 1])].reshape(shape(e)) for e in range(n_ev)],
+                          [pl[int(gl_off[e]):int(gl_off[e + 1])].reshape(shape(e)) for e in range(n_ev)],
+                          n_evidence.reshape(n_ev, int(n_samples)))

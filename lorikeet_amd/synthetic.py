@@ -165,3 +165,35 @@ def ragged(n_regions=1536, seed=4242):
         b.hap_bases = np.ascontiguousarray(np.concatenate(haps))
         parts.append(b)
     return RegionBatch.concat(parts)
+
+
+def make_events(batch, region_ref_hap=None, region_reference_start=None, margin=2):
+    """The variant events of a batch of equal-length (SNV-only) haplotypes, as genotype.Events: one event per position
+    where some haplotype of the region differs from the region's reference haplotype (region_ref_hap, default 0); allele 0
+    is the reference base, then the other bases in the order the haplotypes first show them; every haplotype maps to the
+    allele of its base there; the window is the position on the reference (region_reference_start + position, default
+    0 + position) widened by `margin` (--allele-informative-reads-overlap-margin, 2) on both sides."""
+    from .genotype import Events
+    n = batch.n_regions
+    ref_hap = np.zeros(n, np.int64) if region_ref_hap is None else np.asarray(region_ref_hap, np.int64)
+    ref_start = np.zeros(n, np.int64) if region_reference_start is None else np.asarray(region_reference_start, np.int64)
+    region, n_alleles, start, maps = [], [], [], []
+    for g in range(n):
+        h0, h1 = int(batch.region_hap_off[g]), int(batch.region_hap_off[g + 1])
+        if h1 == h0:
+            continue
+        haps = np.stack([batch.hap_bases[int(batch.hap_off[a]):int(batch.hap_off[a + 1])] for a in range(h0, h1)])
+        ref = haps[int(ref_hap[g])]
+        for pos in np.flatnonzero((haps != ref[None, :]).any(axis=0)):
+            col = haps[:, pos]
+            alleles = [int(ref[pos])]
+            for b in col:
+                if int(b) not in alleles:
+                    alleles.append(int(b))
+            region.append(g)
+            n_alleles.append(len(alleles))
+            start.append(int(ref_start[g]) + int(pos))
+            maps.append([alleles.index(int(b)) for b in col])
+    start = np.asarray(start, np.int64)
+    return Events(region, np.concatenate([[0], np.cumsum(n_alleles, dtype=np.int64)]), start - margin, start + margin,
+                  np.concatenate([np.zeros(0, np.int32)] + [np.asarray(m, np.int32) for m in maps]))
