@@ -559,7 +559,7 @@ int phmm_calculate_cigar(phmm_handle *h, uint32_t n, const uint32_t *ref_off, co
  *   PL              min(round(-10 (GL - max GL)), i32::MAX) with Rust's `as i32` (NaN -> 0): all GLs -inf gives PLs 0
  *                   (Genotype::build_from_likelihoods, src/genotype/genotype_builder.rs:135-152, genotype_likelihoods.rs:55-78)
  * Bit-equal to the reference's operations: no contraction, log10(k) made on the host with std::log10, the host's Jacobian
- * table resident on the device.  Priors, the AF calculation, allele trimming and VCF output stay with the caller.
+ * table resident on the device.  The AF calculation is phmm_allele_frequency below; priors, allele trimming and VCF output stay with the caller.
  *   region_read_off / region_hap_off [n_regions+1], out_off [n_regions+1], likelihoods   as phmm_realign_reads
  *   keep [n_reads] or NULL (every read kept)   0: removed by filter_poorly_modeled_evidence (phmm_engine_compute's keep)
  *   read_sample [n_reads]   in [0, n_samples)
@@ -584,6 +584,67 @@ int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t
                               const uint32_t *event_region, const uint32_t *event_allele_off, const int64_t *event_start,
                               const int64_t *event_end, const int32_t *event_hap_allele, const uint64_t *gl_off, double *gl,
                               int32_t *pl, uint32_t *n_evidence);
+
+/*
+ * The allele-frequency calculation per event: the arithmetic of the reference's GenotypingEngine::calculate_genotypes
+ * (src/genotype/genotyping_engine.rs:80-197) on the PLs phmm_genotype_likelihoods returns, in the same layout, for many
+ * events in ONE call -- what the haplotype caller does per event (haplotype_caller_genotyping_engine.rs:297) and the
+ * activity profile per reference position (haplotype_caller_engine.rs:1060-1085: alleles N / <FAKE_ALT>, ploidy + 1 PLs).
+ *   EM loop         AlleleFrequencyCalculator::calculate (src/model/allele_frequency_calculator.rs:198-379): from the flat
+ *                   -log10(A_e), per sample the normalised log10 posteriors of all G_e genotypes (log10 combination count +
+ *                   PL / -10 + sum of count x log10 frequency, normalised by MathUtils::log10_sum_log10), the effective allele
+ *                   counts summed over samples, the Dirichlet mean weights of prior + counts, until max |Delta count| <= 0.01
+ *   prior class     per allele (:205-217): the reference -> ref_pseudo_count; allele_length == the reference's -> SNP; any
+ *                   other length -> indel (so <FAKE_ALT>, length 0, against N is an indel)
+ *   P(no variant)   the sum over samples of posterior(0/0); with a '*' allele, of min(0, log10_sum_log10) over the genotypes
+ *                   made of the reference and '*' alone (:255-300, :381-403)
+ *   P(absent)       per alt allele, the sum over samples of min(0, log10_sum_log10) over the genotypes without it (:309-343);
+ *                   with A_e == 2 and no '*', P(no variant) itself (:305-307, :348-350)
+ *   mle_count       the final effective counts rounded half away from zero (:352-355), the reference's included
+ *   allele_flags    PLAUSIBLE: log10_p_absent + 1e-10 < -0.1 stand_min_conf (allele_frequency_calculator_result.rs:115-122);
+ *                   OUTPUT: (PLAUSIBLE or the lone alt is <NON_REF>) and not '*' (calculate_output_allele_subset, :390-449)
+ *   qual            -10 log10_confidence + 0.0: log10_p_no_variant, or log10_p_variant_present when the site is MONOMORPHIC
+ *                   (no alt that is PLAUSIBLE and not '*')
+ *   flags           CALLED: calculate_genotypes returns Some (:161-180 with no given alleles); LOW_QUAL: qual < stand_min_conf;
+ *                   MONOMORPHIC; TOO_MANY_ALLELES: A_e > 50 (has_too_many_alternative_alleles), nothing computed, not called;
+ *                   NOT_CONVERGED: the EM loop met the device's cap of 10 000 iterations (the reference has none)
+ * The device assumes what a caller without deletion state and without given alleles has: no event is covered by an upstream
+ * deletion (record_deletions :185, is_vc_covered_by_deletion :451), no allele is forced.  A caller with that state sets its
+ * covered events' outputs aside (every alt is then spurious: nothing is output and the site is MONOMORPHIC, so QUAL comes
+ * from log10_p_variant_present) and adds its forced alleles to those with OUTPUT.  n_samples == 0: no event is called.
+ * Not bit-equal: pow / log10 inside the loop are the device's (ocml) and the sums run in a fixed order of their own; results
+ * agree with the reference's operations to about 1e-13 relative and are bit-identical from run to run and whatever the batch.
+ *   event_allele_off [n_events+1]   A_e = off[e+1] - off[e] alleles, allele 0 the reference; 2 <= A_e
+ *   allele_length [off[n]]          Allele::length() (0 for a symbolic allele)
+ *   allele_kind [off[n]] or NULL    PHMM_AF_KIND_*; allele 0 plain, at most one '*'; NULL: every allele plain
+ *   pl_off [n_events+1], pl         as phmm_genotype_likelihoods' gl_off / pl: n_samples x G_e PLs, sample-major [s][g]
+ *   *_pseudo_count                  AlleleFrequencyCalculator::new (make_calculator :53-75: ref = snp_het / het_stdev^2,
+ *                                   snp = snp_het x ref, indel = indel_het x ref)
+ *   stand_min_conf                  --standard-min-confidence-threshold-for-calling
+ *   log10_p_no_variant, log10_p_variant_present (log10_one_minus_pow10 of the former), qual, flags [n_events];
+ *   iterations [n_events] or NULL   EM iterations taken
+ *   log10_p_absent, mle_count [off[n]], allele_flags [off[n]] or NULL: per allele, the reference's slot 0.0 / its count / 0
+ * Events not computed (TOO_MANY_ALLELES, or n_samples == 0) get 0 everywhere but in flags.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offending event): a required array NULL, offsets not
+ * monotonic, ploidy 0, A_e < 2, G_e > 1 024 where A_e <= 50, allele 0 not plain, more than one '*' allele, an unknown kind, a
+ * pl_off slot smaller than n_samples x G_e.  n_events == 0 returns PHMM_OK.  One thread per handle.
+ */
+#define PHMM_AF_KIND_PLAIN 0
+#define PHMM_AF_KIND_SPAN_DEL 1
+#define PHMM_AF_KIND_NON_REF 2
+#define PHMM_AF_CALLED 1u
+#define PHMM_AF_LOW_QUAL 2u
+#define PHMM_AF_MONOMORPHIC 4u
+#define PHMM_AF_TOO_MANY_ALLELES 8u
+#define PHMM_AF_NOT_CONVERGED 16u
+#define PHMM_AF_ALLELE_PLAUSIBLE 1u
+#define PHMM_AF_ALLELE_OUTPUT 2u
+int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples, uint32_t ploidy,
+                          const uint32_t *event_allele_off, const uint32_t *allele_length, const uint8_t *allele_kind,
+                          const uint64_t *pl_off, const int32_t *pl, double ref_pseudo_count, double snp_pseudo_count,
+                          double indel_pseudo_count, double stand_min_conf, double *log10_p_no_variant,
+                          double *log10_p_variant_present, double *log10_p_absent, int64_t *mle_count,
+                          uint8_t *allele_flags, double *qual, uint32_t *flags, uint32_t *iterations);
 
 /*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).

@@ -74,6 +74,18 @@ pub struct phmm_plan_info {
 /// (src/haplotype/haplotype_caller_engine.rs:1339-1345 returns before it gets there)
 pub const PHMM_REGION_SKIP_SINGLE_ALLELE: c_uint = 1;
 
+/// `phmm_allele_frequency`: allele kinds, per-event flags, per-allele flags
+pub const PHMM_AF_KIND_PLAIN: c_int = 0;
+pub const PHMM_AF_KIND_SPAN_DEL: c_int = 1;
+pub const PHMM_AF_KIND_NON_REF: c_int = 2;
+pub const PHMM_AF_CALLED: c_uint = 1;
+pub const PHMM_AF_LOW_QUAL: c_uint = 2;
+pub const PHMM_AF_MONOMORPHIC: c_uint = 4;
+pub const PHMM_AF_TOO_MANY_ALLELES: c_uint = 8;
+pub const PHMM_AF_NOT_CONVERGED: c_uint = 16;
+pub const PHMM_AF_ALLELE_PLAUSIBLE: c_uint = 1;
+pub const PHMM_AF_ALLELE_OUTPUT: c_uint = 2;
+
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
 /// (src/reads/alignment_utils.rs:52-58, src/model/allele_likelihoods.rs:17)
 #[repr(C)]
@@ -577,6 +589,31 @@ extern "C" {
         gl: *mut f64,
         pl: *mut i32,
         n_evidence: *mut u32,
+    ) -> c_int;
+    /// GenotypingEngine::calculate_genotypes' arithmetic per event (genotyping_engine.rs:80-197): the EM allele-frequency
+    /// calculation on the PLs above, P(no variant), P(allele absent), MLE counts, the output subset and QUAL
+    pub fn phmm_allele_frequency(
+        h: *mut phmm_handle,
+        n_events: u32,
+        n_samples: u32,
+        ploidy: u32,
+        event_allele_off: *const u32,
+        allele_length: *const u32,
+        allele_kind: *const u8,
+        pl_off: *const u64,
+        pl: *const i32,
+        ref_pseudo_count: f64,
+        snp_pseudo_count: f64,
+        indel_pseudo_count: f64,
+        stand_min_conf: f64,
+        log10_p_no_variant: *mut f64,
+        log10_p_variant_present: *mut f64,
+        log10_p_absent: *mut f64,
+        mle_count: *mut i64,
+        allele_flags: *mut u8,
+        qual: *mut f64,
+        flags: *mut u32,
+        iterations: *mut u32,
     ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;

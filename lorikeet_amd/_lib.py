@@ -30,6 +30,9 @@ PHMM_SW_SOFTCLIP, PHMM_SW_INDEL, PHMM_SW_LEADING_INDEL, PHMM_SW_IGNORE = 0, 1, 2
 PHMM_SW_NO_REFERENCE = 0xffffffff
 PHMM_PROJECT_REALIGNED, PHMM_PROJECT_UNCHANGED = 0, 1
 PHMM_REGION_SKIP_SINGLE_ALLELE = 1
+PHMM_AF_KIND_PLAIN, PHMM_AF_KIND_SPAN_DEL, PHMM_AF_KIND_NON_REF = 0, 1, 2
+PHMM_AF_CALLED, PHMM_AF_LOW_QUAL, PHMM_AF_MONOMORPHIC, PHMM_AF_TOO_MANY_ALLELES, PHMM_AF_NOT_CONVERGED = 1, 2, 4, 8, 16
+PHMM_AF_ALLELE_PLAUSIBLE, PHMM_AF_ALLELE_OUTPUT = 1, 2
 
 class EngineConfig(C.Structure):
     """phmm_engine_config (include/phmm.h)."""
@@ -122,6 +125,9 @@ SYMBOLS = [
     ("phmm_genotype_likelihoods", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u64p, f64p, u8p, u32p, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32), u64p, f64p, C.POINTER(C.c_int32), u32p]),
+    ("phmm_allele_frequency", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u8p, u64p, C.POINTER(C.c_int32),
+                                        C.c_double, C.c_double, C.c_double, C.c_double, f64p, f64p, f64p, C.POINTER(C.c_int64), u8p,
+                                        f64p, u32p, u32p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),

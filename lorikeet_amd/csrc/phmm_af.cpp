@@ -1,0 +1,284 @@
+// phmm_allele_frequency (include/phmm.h): host side -- validation, prior classes, the genotype tables with their log10
+// combination counts, staging.  The arithmetic runs on the device (phmm_af_kernels.hip); there is no CPU path here.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "phmm_af_internal.hpp"
+#include "phmm_host.hpp"
+
+using namespace phmm;
+
+namespace {
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+struct DevGuard {
+    int prev = -1, dev;
+    explicit DevGuard(int d) : dev(d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DevGuard() {
+        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+};
+
+bool ok(phmm_handle *h, hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    h->err = std::string(what) + ": " + hipGetErrorString(e);
+    h->err_code = PHMM_ERR_HIP;
+    return false;
+}
+
+int fail(phmm_handle *h, const std::string &msg) {
+    h->err = "phmm_allele_frequency: " + msg;
+    return h->err_code = PHMM_ERR_INVALID_ARG;
+}
+
+// MathUtils::log10_factorial (math_utils.rs:133-135): ln_gamma(n + 1) * LOG10_E
+double log10_factorial(double n) { return std::lgamma(n + 1.0) * std::log10(M_E); }
+
+uint32_t genotypes_per_lane(uint32_t G) { return G <= 64 ? 1 : G <= 256 ? 4 : G <= 512 ? 8 : 16; }
+
+}  // namespace
+
+extern "C" {
+
+int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples, uint32_t ploidy, const uint32_t *event_allele_off,
+                          const uint32_t *allele_length, const uint8_t *allele_kind, const uint64_t *pl_off, const int32_t *pl,
+                          double ref_pseudo_count, double snp_pseudo_count, double indel_pseudo_count, double stand_min_conf,
+                          double *log10_p_no_variant, double *log10_p_variant_present, double *log10_p_absent, int64_t *mle_count,
+                          uint8_t *allele_flags, double *qual, uint32_t *flags, uint32_t *iterations) {
+    if (!h) return PHMM_ERR_INVALID_ARG;
+    try {
+        h->err_code = PHMM_OK;
+        if (!n_events) return PHMM_OK;
+        // ---- arguments: everything is checked before anything is written ----------------------------------------------------
+        if (!event_allele_off || !allele_length || !pl_off || !log10_p_no_variant || !log10_p_variant_present ||
+            !log10_p_absent || !mle_count || !qual || !flags)
+            return fail(h, "null array");
+        if (!ploidy) return fail(h, "ploidy must be at least 1");
+        if (n_samples && !pl) return fail(h, "null array");
+        std::vector<uint32_t> computed, G(n_events, 0);
+        std::vector<int32_t> span_del(n_events, -1);
+        uint32_t max_alleles = 0;
+        for (uint32_t e = 0; e < n_events; ++e) {
+            const std::string ev = "event " + std::to_string(e) + ": ";
+            if (event_allele_off[e + 1] < event_allele_off[e]) return fail(h, ev + "event_allele_off not monotonic");
+            if (pl_off[e + 1] < pl_off[e]) return fail(h, ev + "pl_off not monotonic");
+            const uint32_t a0 = event_allele_off[e], A = event_allele_off[e + 1] - a0;
+            if (A < 2) return fail(h, ev + "fewer than 2 alleles");
+            if (allele_kind) {
+                if (allele_kind[a0] != PHMM_AF_KIND_PLAIN) return fail(h, ev + "allele 0 (the reference) is not plain");
+                for (uint32_t a = 1; a < A; ++a) {
+                    const uint8_t k = allele_kind[a0 + a];
+                    if (k > PHMM_AF_KIND_NON_REF) return fail(h, ev + "allele " + std::to_string(a) + ": unknown kind");
+                    if (k == PHMM_AF_KIND_SPAN_DEL) {
+                        if (span_del[e] >= 0) return fail(h, ev + "more than one '*' allele");
+                        span_del[e] = (int32_t)a;
+                    }
+                }
+            }
+            if (A > AF_MAX_ALLELES) continue;  // PHMM_AF_TOO_MANY_ALLELES: not called, no genotypes enumerated
+            G[e] = phmm_genotype_count(ploidy, A);
+            if (G[e] > AF_MAX_GENOTYPES)
+                return fail(h, ev + std::to_string(G[e]) + " genotypes, more than " + std::to_string(AF_MAX_GENOTYPES));
+            if (pl_off[e + 1] - pl_off[e] < (uint64_t)n_samples * G[e]) return fail(h, ev + "pl_off slot smaller than n_samples x genotypes");
+            if (n_samples) {
+                computed.push_back(e);
+                max_alleles = std::max(max_alleles, A);
+            }
+        }
+
+        // ---- events that are not computed: too many alleles, or no samples -------------------------------------------------
+        for (uint32_t e = 0; e < n_events; ++e) {
+            const uint32_t A = event_allele_off[e + 1] - event_allele_off[e];
+            if (A <= AF_MAX_ALLELES && n_samples) continue;
+            log10_p_no_variant[e] = log10_p_variant_present[e] = qual[e] = 0.0;
+            flags[e] = A > AF_MAX_ALLELES ? PHMM_AF_TOO_MANY_ALLELES : 0u;
+            if (iterations) iterations[e] = 0;
+            for (uint32_t a = event_allele_off[e]; a < event_allele_off[e + 1]; ++a) {
+                log10_p_absent[a] = 0.0;
+                mle_count[a] = 0;
+                if (allele_flags) allele_flags[a] = 0;
+            }
+        }
+        const uint32_t n_c = (uint32_t)computed.size();
+        if (!n_c) return PHMM_OK;
+
+        // ---- the genotypes of (ploidy, most alleles): the index order of fewer alleles is a prefix of it ------------------
+        const auto &T = genotype_table_of(h, ploidy, max_alleles);
+        const size_t n_gt = T.first.size() - 1;
+        std::vector<double> log10_comb(n_gt);
+        std::vector<uint64_t> gt_alleles(n_gt, 0);
+        const double log10_ploidy_factorial = log10_factorial((double)ploidy);
+        for (size_t g = 0; g < n_gt; ++g) {
+            double s = 0.0;
+            for (uint32_t c = T.first[g]; c < T.first[g + 1]; ++c) {
+                s += log10_factorial((double)(T.second[c] >> 16));
+                gt_alleles[g] |= 1ull << (T.second[c] & 0xffffu);
+            }
+            log10_comb[g] = log10_ploidy_factorial - s;  // GenotypeAlleleCounts::log10_combination_count
+        }
+        std::vector<double> neg_log10_alleles(AF_MAX_ALLELES + 1, 0.0);
+        for (uint32_t a = 1; a <= AF_MAX_ALLELES; ++a) neg_log10_alleles[a] = -std::log10((double)a);
+
+        // ---- the computed events, densely: alleles with their prior pseudo counts, PLs ------------------------------------
+        std::vector<uint32_t> c_allele_off(n_c + 1, 0), c_G(n_c);
+        std::vector<int32_t> c_span_del(n_c);
+        std::vector<uint64_t> c_pl_off(n_c);
+        uint64_t n_pl = 0;
+        for (uint32_t i = 0; i < n_c; ++i) {
+            const uint32_t e = computed[i];
+            c_allele_off[i + 1] = c_allele_off[i] + (event_allele_off[e + 1] - event_allele_off[e]);
+            c_G[i] = G[e];
+            c_span_del[i] = span_del[e];
+            c_pl_off[i] = n_pl;
+            n_pl += (uint64_t)n_samples * G[e];
+        }
+        const uint32_t n_al = c_allele_off[n_c];
+        std::vector<double> prior(n_al);
+        std::vector<uint8_t> kind(n_al, PHMM_AF_KIND_PLAIN);
+        for (uint32_t i = 0; i < n_c; ++i) {
+            const uint32_t e = computed[i], a0 = event_allele_off[e], A = c_allele_off[i + 1] - c_allele_off[i];
+            for (uint32_t a = 0; a < A; ++a) {
+                // allele_frequency_calculator.rs:205-217: reference; length of the reference -> SNP; otherwise indel
+                prior[c_allele_off[i] + a] = a == 0                                  ? ref_pseudo_count
+                                             : allele_length[a0 + a] == allele_length[a0] ? snp_pseudo_count
+                                                                                          : indel_pseudo_count;
+                if (allele_kind) kind[c_allele_off[i] + a] = allele_kind[a0 + a];
+            }
+        }
+        // the work lists: per genotypes-per-lane class, first the events of one wave, then the events of a workgroup
+        std::vector<uint32_t> work;
+        uint32_t cls_off[4][3] = {};  // [class][wave begin, wave count, block count]
+        const uint32_t classes[4] = {1, 4, 8, 16};
+        for (int c = 0; c < 4; ++c) {
+            cls_off[c][0] = (uint32_t)work.size();
+            for (int block = 0; block < 2; ++block) {
+                for (uint32_t i = 0; i < n_c; ++i) {
+                    if (genotypes_per_lane(c_G[i]) != classes[c]) continue;
+                    uint32_t S = 64;
+                    if (classes[c] == 1) {
+                        S = 1;
+                        while (S < c_G[i]) S <<= 1;
+                    }
+                    const uint32_t passes = (n_samples + 64 / S - 1) / (64 / S);
+                    if ((passes >= AF_BLOCK_PASSES) == (block == 1)) work.push_back(i);
+                }
+                cls_off[c][1 + block] = (uint32_t)work.size() - cls_off[c][0] - (block ? cls_off[c][1] : 0);
+            }
+        }
+
+        DevGuard dg(h->device);
+        auto &W = h->afwork;
+        hipStream_t S = h->streams[0];
+        // ---- staging: inputs, then the outputs -----------------------------------------------------------------------------
+        size_t o = 0;
+        auto place = [&](size_t bytes) {
+            const size_t at = o;
+            o += up256(bytes);
+            return at;
+        };
+        const size_t o_wk = place(4ull * work.size()), o_ao = place(4ull * (n_c + 1)), o_gc = place(4ull * n_c),
+                     o_sd = place(4ull * n_c), o_po = place(8ull * n_c), o_pl = place(4ull * n_pl), o_pr = place(8ull * n_al),
+                     o_kd = place(n_al), o_co = place(4ull * (n_gt + 1)), o_c = place(4ull * T.second.size()),
+                     o_lc = place(8ull * n_gt), o_ga = place(8ull * n_gt), o_nl = place(8ull * (AF_MAX_ALLELES + 1)), in_bytes = o;
+        const size_t o_pnv = place(8ull * n_c), o_pvp = place(8ull * n_c), o_q = place(8ull * n_c), o_fl = place(4ull * n_c),
+                     o_it = place(4ull * n_c), o_abs = place(8ull * n_al), o_mle = place(8ull * n_al), o_af = place(n_al), total = o;
+        if (W.cap < total) {
+            (void)hipStreamSynchronize(S);
+            if (W.dev) (void)hipFree(W.dev);
+            if (W.host) (void)hipHostFree(W.host);
+            W.dev = W.host = nullptr;
+            W.cap = 0;
+            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
+            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(allele-frequency staging)") ||
+                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(allele-frequency staging)"))
+                return PHMM_ERR_HIP;
+            W.cap = cap;
+        }
+        auto put = [&](size_t at, const void *src, size_t bytes) {
+            if (bytes) memcpy(W.host + at, src, bytes);
+        };
+        put(o_wk, work.data(), 4ull * work.size());
+        put(o_ao, c_allele_off.data(), 4ull * (n_c + 1));
+        put(o_gc, c_G.data(), 4ull * n_c);
+        put(o_sd, c_span_del.data(), 4ull * n_c);
+        put(o_po, c_pl_off.data(), 8ull * n_c);
+        for (uint32_t i = 0; i < n_c; ++i) put(o_pl + 4 * c_pl_off[i], pl + pl_off[computed[i]], 4ull * n_samples * c_G[i]);
+        put(o_pr, prior.data(), 8ull * n_al);
+        put(o_kd, kind.data(), n_al);
+        put(o_co, T.first.data(), 4ull * (n_gt + 1));
+        put(o_c, T.second.data(), 4ull * T.second.size());
+        put(o_lc, log10_comb.data(), 8ull * n_gt);
+        put(o_ga, gt_alleles.data(), 8ull * n_gt);
+        put(o_nl, neg_log10_alleles.data(), 8ull * (AF_MAX_ALLELES + 1));
+        h->stat_staged_bytes += in_bytes;
+
+        AfParams p{};
+        p.n_samples = n_samples;
+        p.allele_off = (const uint32_t *)(W.dev + o_ao);
+        p.genotype_count = (const uint32_t *)(W.dev + o_gc);
+        p.span_del = (const int32_t *)(W.dev + o_sd);
+        p.pl_off = (const uint64_t *)(W.dev + o_po);
+        p.pl = (const int32_t *)(W.dev + o_pl);
+        p.prior = (const double *)(W.dev + o_pr);
+        p.kind = (const uint8_t *)(W.dev + o_kd);
+        p.gt_comp_off = (const uint32_t *)(W.dev + o_co);
+        p.gt_comp = (const uint32_t *)(W.dev + o_c);
+        p.gt_log10_comb = (const double *)(W.dev + o_lc);
+        p.gt_alleles = (const uint64_t *)(W.dev + o_ga);
+        p.neg_log10_alleles = (const double *)(W.dev + o_nl);
+        p.stand_min_conf = stand_min_conf;
+        p.log_10 = std::log(10.0);
+        p.inv_log_10 = 1.0 / p.log_10;
+        p.log1mexp_threshold = std::log(0.5);
+        p.log10_p_no_variant = (double *)(W.dev + o_pnv);
+        p.log10_p_variant_present = (double *)(W.dev + o_pvp);
+        p.qual = (double *)(W.dev + o_q);
+        p.flags = (uint32_t *)(W.dev + o_fl);
+        p.iterations = (uint32_t *)(W.dev + o_it);
+        p.log10_p_absent = (double *)(W.dev + o_abs);
+        p.mle_count = (int64_t *)(W.dev + o_mle);
+        p.allele_flags = (uint8_t *)(W.dev + o_af);
+        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes, hipMemcpyHostToDevice, S), "H2D allele frequency")) return PHMM_ERR_HIP;
+        for (int c = 0; c < 4; ++c) {
+            p.work = (const uint32_t *)(W.dev + o_wk) + cls_off[c][0];
+            p.n_wave_events = cls_off[c][1];
+            p.n_block_events = cls_off[c][2];
+            if (!ok(h, launch_af(p, classes[c], S), "phmm_af_kernel")) return PHMM_ERR_HIP;
+        }
+        if (!ok(h, hipMemcpyAsync(W.host + o_pnv, W.dev + o_pnv, total - o_pnv, hipMemcpyDeviceToHost, S), "D2H allele frequency") ||
+            !ok(h, hipStreamSynchronize(S), "sync(allele frequency)"))
+            return PHMM_ERR_HIP;
+        const double *r_pnv = (const double *)(W.host + o_pnv), *r_pvp = (const double *)(W.host + o_pvp),
+                     *r_q = (const double *)(W.host + o_q), *r_abs = (const double *)(W.host + o_abs);
+        const uint32_t *r_fl = (const uint32_t *)(W.host + o_fl), *r_it = (const uint32_t *)(W.host + o_it);
+        const int64_t *r_mle = (const int64_t *)(W.host + o_mle);
+        const uint8_t *r_af = (const uint8_t *)(W.host + o_af);
+        for (uint32_t i = 0; i < n_c; ++i) {
+            const uint32_t e = computed[i], a0 = event_allele_off[e], c0 = c_allele_off[i], A = c_allele_off[i + 1] - c0;
+            log10_p_no_variant[e] = r_pnv[i];
+            log10_p_variant_present[e] = r_pvp[i];
+            qual[e] = r_q[i];
+            flags[e] = r_fl[i];
+            if (iterations) iterations[e] = r_it[i];
+            memcpy(log10_p_absent + a0, r_abs + c0, 8ull * A);
+            memcpy(mle_count + a0, r_mle + c0, 8ull * A);
+            if (allele_flags) memcpy(allele_flags + a0, r_af + c0, A);
+        }
+        return PHMM_OK;
+    } catch (const std::bad_alloc &) {
+        h->err = "phmm_allele_frequency: out of host memory";
+        return h->err_code = PHMM_ERR_NO_MEMORY;
+    } catch (const std::exception &e) {
+        h->err = std::string("phmm_allele_frequency: ") + e.what();
+        return h->err_code = PHMM_ERR_INTERNAL;
+    }
+}
+
+}  // extern "C"

@@ -398,6 +398,8 @@ void phmm_destroy(phmm_handle *h) {
     if (h->gwork.dev) (void)hipFree(h->gwork.dev);
     if (h->gwork.host) (void)hipHostFree(h->gwork.host);
     if (h->gwork.d_jacobian) (void)hipFree(h->gwork.d_jacobian);
+    if (h->afwork.dev) (void)hipFree(h->afwork.dev);
+    if (h->afwork.host) (void)hipHostFree(h->afwork.host);
     for (int c = 0; c < phmm_handle::SwWork::kMaxChunks; ++c)
         for (hipEvent_t e : {h->swork.ev_in[c], h->swork.ev_out[c], h->swork.ev_k0[c], h->swork.ev_k1[c]})
             if (e) (void)hipEventDestroy(e);

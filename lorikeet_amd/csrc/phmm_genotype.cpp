@@ -89,6 +89,12 @@ void genotype_table(uint32_t ploidy, uint32_t n_alleles, std::vector<uint32_t> *
 
 }  // namespace
 
+const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &genotype_table_of(phmm_handle *h, uint32_t ploidy, uint32_t n_alleles) {
+    auto &T = h->gwork.tables[(uint64_t)ploidy << 32 | n_alleles];
+    if (T.first.empty()) genotype_table(ploidy, n_alleles, &T.first, &T.second);
+    return T;
+}
+
 extern "C" {
 
 uint32_t phmm_genotype_count(uint32_t ploidy, uint32_t n_alleles) {
@@ -171,8 +177,7 @@ int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t
         }
 
         // ---- the genotypes of (ploidy, most alleles): the index order of fewer alleles is a prefix of it ------------------
-        auto &T = h->gwork.tables[(uint64_t)ploidy << 32 | max_alleles];
-        if (T.first.empty()) genotype_table(ploidy, max_alleles, &T.first, &T.second);
+        const auto &T = genotype_table_of(h, ploidy, max_alleles);
         std::vector<double> log10_k(ploidy + 1, 0.0);
         for (uint32_t k = 1; k <= ploidy; ++k) log10_k[k] = std::log10((double)k);
 

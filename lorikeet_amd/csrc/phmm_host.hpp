@@ -131,6 +131,10 @@ struct phmm_handle {
         // the genotypes of (ploidy, alleles) in index order, by (ploidy << 32 | alleles): [G + 1] offsets, (allele | count << 16)
         std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
     } gwork;
+    struct AfWork {  // phmm_allele_frequency (phmm_af.cpp): grow-only staging
+        char *dev = nullptr, *host = nullptr;
+        size_t cap = 0;
+    } afwork;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit
@@ -140,6 +144,11 @@ struct phmm_handle {
     bool defer_d2h = false;           // see eager_d2h(): set around pipelined chunks and combined flushes
     std::once_flag comb_once;
 };
+
+// The genotypes of (ploidy, n_alleles) in the reference's index order, from the handle's cache h->gwork.tables (made on first
+// use; phmm_genotype.cpp): [G + 1] component offsets, components (allele | count << 16) with the alleles ascending.  Only for
+// phmm_genotype_count(ploidy, n_alleles) <= 1 024.
+const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &genotype_table_of(phmm_handle *h, uint32_t ploidy, uint32_t n_alleles);
 
 namespace phmm_host {
 

@@ -104,3 +104,58 @@ def genotype_likelihoods(engine, batch, likelihoods, keep, read_start, read_end_
     return GenotypeResult([gl[int(gl_off[e]):int(gl_off[e + 1])].reshape(shape(e)) for e in range(n_ev)],
                           [pl[int(gl_off[e]):int(gl_off[e + 1])].reshape(shape(e)) for e in range(n_ev)],
                           n_evidence.reshape(n_ev, int(n_samples)))
+
+
+# ---- the allele-frequency calculation (phmm_allele_frequency) ------------------------------------------------------------
+
+def pseudo_counts(snp_het=0.001, indel_het=0.000125, het_stdev=0.01):
+    """(ref, snp, indel) pseudo counts as AlleleFrequencyCalculator::make_calculator makes them
+    (src/model/allele_frequency_calculator.rs:53-75) from --snp-heterozygosity, --indel-heterozygosity and
+    --heterozygosity-stdev (defaults: src/cli.rs:1509-1526)."""
+    ref = snp_het / (het_stdev ** 2.0)
+    return ref, snp_het * ref, indel_het * ref
+
+
+class AFResult:
+    """Per event e: log10_p_no_variant[e], log10_p_variant_present[e], qual[e], flags[e] (PHMM_AF_*), iterations[e];
+    per event the arrays over its alleles (reference first): log10_p_absent[e] (reference slot 0.0), mle_count[e],
+    allele_flags[e] (PHMM_AF_ALLELE_*)."""
+
+    def __init__(self, allele_off, pnv, pvp, absent, mle, aflags, qual, flags, iterations):
+        self.log10_p_no_variant, self.log10_p_variant_present, self.qual = pnv, pvp, qual
+        self.flags, self.iterations = flags, iterations
+        cut = lambda a: [a[int(allele_off[e]):int(allele_off[e + 1])] for e in range(len(allele_off) - 1)]  # noqa: E731
+        self.log10_p_absent, self.mle_count, self.allele_flags = cut(absent), cut(mle), cut(aflags)
+
+    def called(self, e):
+        return bool(self.flags[e] & _lib.PHMM_AF_CALLED)
+
+
+def allele_frequency(engine, pl, pl_off=None, allele_off=None, allele_length=None, allele_kind=None, n_samples=1, ploidy=2,
+                     pseudo_counts=pseudo_counts(), stand_min_conf=30.0):
+    """The allele-frequency step of calculate_genotypes for a batch of events (phmm_allele_frequency, include/phmm.h).
+    `pl`: the PLs, flat with pl_off [n_events + 1] (n_samples x G_e per event, sample-major), or a GenotypeResult of
+    genotype_likelihoods (pl_off then comes from it); allele_off [n_events + 1]; allele_length: Allele::length() per allele;
+    allele_kind: PHMM_AF_KIND_* per allele or None (all plain); pseudo_counts: (ref, snp, indel)."""
+    if isinstance(pl, GenotypeResult):
+        n_samples = np.shape(pl.pl[0])[0] if pl.pl else n_samples
+        parts = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in pl.pl]
+        pl_off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.uint64)
+        pl = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    pl = np.ascontiguousarray(pl, np.int32)
+    pl_off = np.ascontiguousarray(pl_off, np.uint64)
+    ao = np.ascontiguousarray(allele_off, np.uint32)
+    ln = np.ascontiguousarray(allele_length, np.uint32)
+    kd = None if allele_kind is None else np.ascontiguousarray(allele_kind, np.uint8)
+    n_ev, n_al = len(ao) - 1, int(ao[-1]) if len(ao) else 0
+    pnv, pvp, qual = np.zeros(n_ev), np.zeros(n_ev), np.zeros(n_ev)
+    flags, iters = np.zeros(n_ev, np.uint32), np.zeros(n_ev, np.uint32)
+    absent, mle, aflags = np.zeros(n_al), np.zeros(n_al, np.int64), np.zeros(n_al, np.uint8)
+    ref, snp, indel = (float(x) for x in pseudo_counts)
+    code = engine.lib.phmm_allele_frequency(
+        engine._h, n_ev, int(n_samples), int(ploidy), _p(ao, _lib.u32p), _p(ln, _lib.u32p), _p(kd, _lib.u8p), _p(pl_off, _lib.u64p),
+        _p(pl, _i32p), ref, snp, indel, float(stand_min_conf), _p(pnv, _lib.f64p), _p(pvp, _lib.f64p), _p(absent, _lib.f64p),
+        _p(mle, _i64p), _p(aflags, _lib.u8p), _p(qual, _lib.f64p), _p(flags, _lib.u32p), _p(iters, _lib.u32p))
+    if code != _lib.PHMM_OK:
+        raise PhmmError(code, engine.last_error())
+    return AFResult(ao, pnv, pvp, absent, mle, aflags, qual, flags, iters)
