@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- PairHMM cell-updates/s (GCUPS) on MI355X, the metric BASELINE.json names.
 
-  python bench.py --gpus 1 --steps K --warmup W
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path (phmm_batch_launch: the forward kernels, nothing else) over one batch of
 synthetic assembly regions already resident in HBM.  `--dump-outputs DIR` writes the likelihoods of the last timed step to
@@ -12,7 +12,11 @@ DIR/*.npy (dump_outputs()); the inputs depend on the arguments alone, so two bui
 haplotypes, 150 bp reads, 300 bp haplotypes -- i.e. SURVEY.md 8(d)'s batched form of config 2; rank r draws its own
 regions (seed base+r): regions shard across GPUs with no collective, "weak" scaling.  Rank 0 prints ONE JSON line.
 
-Rows next to it on the same line (BASELINE.json configs[2..4]; all ranks take part, rank 0 reports):
+A plain run does only what `value` needs: it sets up, warms up, times the steps, dumps (if asked) and prints the line, whose
+roofline figures come from the timed launches themselves.  `--full` adds everything below (minutes of work: the other
+configurations, precisions and call shapes, the oracle checks and the CPU baselines); the headline fields are the same.
+
+Rows next to it on the same line with --full (BASELINE.json configs[2..4]; all ranks take part, rank 0 reports):
   config3_10k   the SAME 10 000-region set (seed 20250928, read lengths mixed {100,150,250}) at every N, sharded over the
                 N ranks in contiguous ranges balanced by cells (no collective): strong scaling -- regions/s, GCUPS,
                 per-rank cells, imbalance, dominant kernel and its launch time, oracle sample check
@@ -22,7 +26,7 @@ Rows next to it on the same line (BASELINE.json configs[2..4]; all ranks take pa
   single_region / engine_call / host_calls   one region per launch; the engine-level call; the reference's call
                 granularity from host threads (PCIe included)
 
-Objects:
+Objects (cpu_baseline and the oracle_sample check only with --full):
   roofline      algorithmic HBM bytes (5*sum R + sum H + 8*Nr*Nh per region) per launch / the dominant
                 kernel's mean launch duration (HIP events on the launch stream), vs 8 TB/s.  `traffic`, `l2_hit_rate`
                 and `valu_issue` come from rocprofv3 PMC passes of this very command committed in
@@ -75,8 +79,12 @@ def parse():
     ap.add_argument("--flush-caches", action="store_true",
                     help="PMC calibration only: overwrite a 1 GiB buffer before every launch so that no input byte "
                          "survives in L2 / Infinity Cache from the previous launch (the timing then includes the fill)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every other row (config3_10k, config5_256, ragged, f32_first, single_region, engine_call, host_calls, "
+                         "smith_waterman, realign_to_best), the oracle sample checks and the CPU baselines; a plain run times the "
+                         "main workload only")
     ap.add_argument("--main-only", action="store_true",
-                    help="only the timed loop (no extra rows, no cpu_baseline): for PMC passes")
+                    help="only the timed loop even with --full (what a plain run does): for PMC passes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed loop's last step computed (the likelihoods, float64) to DIR/*.npy, so that two "
                          "builds can be compared output for output; see dump_outputs()")
@@ -536,7 +544,7 @@ def main():
     os.environ.setdefault("PHMM_REGION_OWN_QUEUE", "0")
     D = Dist(a)
     torch, dev, rank, world = D.torch, D.dev, D.rank, D.world
-    extras = not a.main_only
+    extras = a.full and not a.main_only
 
     from lorikeet_amd import HipPairHMMEngine
     strong = None
@@ -1097,7 +1105,7 @@ def main():
             return float(x)
 
     single = f32_row = engine_row = calls_row = ragged_row = sw_row = None
-    # (BENCH_ROWS=ragged,sw ... : only these secondary rows -- developer runs; the driver's run has them all)
+    # (BENCH_ROWS=ragged,sw ... : only these secondary rows of a --full run -- developer runs; unset, --full has them all)
     only_rows = set(filter(None, os.environ.get("BENCH_ROWS", "").split(",")))
     want = lambda name: not only_rows or name in only_rows  # noqa: E731
     if rank == 0 and extras:

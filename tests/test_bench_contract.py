@@ -80,6 +80,17 @@ def test_the_compact_line_holds_the_contract_and_every_row_in_four_kilobytes():
     assert os.path.exists(os.path.join(ROOT, line["notes"]))
 
 
+def test_the_extra_rows_are_opt_in(monkeypatch):
+    """A plain run times the main workload only; --full brings back every other row, the oracle checks and the CPU baselines."""
+    import sys
+    argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+    monkeypatch.setattr(sys, "argv", argv)
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", argv + ["--full"])
+    a = bench.parse()
+    assert a.full is True and a.main_only is False and (a.steps, a.warmup) == (20, 5)
+
+
 import pytest  # noqa: E402
 
 
