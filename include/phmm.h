@@ -666,9 +666,15 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
  * staging so far), "rescue_passes" (batches that needed the exact pass below -600), "sw_kernel_us" / "sw_backtrack_bytes" /
  * "sw_clock_mhz" (device time of the last phmm_sw_align's kernels by HIP events, the backtrack bytes they stored, the shader
  * clock one of their blocks saw), "sw_second_pass" (alignments of the last aligner call whose walk met a gap behind the
- * tags-only sweep and which the full instance aligned again; 0 when the call took one pass), "region_sw_all" (region calls that
- * aligned every pair beside the PairHMM kernels so far), "server_jobs" / "server_launches" / "server_broken" (the device's region
- * server: calls it has taken, times it was launched, whether it gave up); unknown names give 0.
+ * tags-only sweep and which the full instance aligned again; 0 when the call took one pass), "sw_instance" (which compiled
+ * aligner kernel the first launch of the last phmm_sw_align / _indexed / phmm_realign_* / phmm_calculate_cigar call was: columns
+ * -- rows, for the sweep along the alternate -- per lane K in bits 0-7, lanes per alignment L in bits 8-15, bit 16 = the sweep
+ * along the alternate, bits 17-19 = variant (1 wide weights | 2 rows in device memory | 4 the tags-only first pass), bits 32-63 =
+ * strips of L x K columns; phmm_region_compute's own launches do not set it), "sw_instance_second" (the same for the second pass
+ * of that call: the instance that redid the first of its lists of alignments with gaps, 0 when none was redone; decoder:
+ * lorikeet_amd/smith_waterman.py decode_instance), "region_sw_all" (region calls that aligned every pair beside the PairHMM
+ * kernels so far), "server_jobs" / "server_launches" / "server_broken" (the device's region server: calls it has taken, times it
+ * was launched, whether it gave up); unknown names give 0.
  */
 int phmm_set_switch(phmm_handle *h, const char *name, int value);
 uint64_t phmm_get_stat(phmm_handle *h, const char *name);

@@ -2495,6 +2495,8 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name) {
     else if (n == "sw_kernel_us") return h->swork.last_kernel_us;
     else if (n == "sw_backtrack_bytes") return h->swork.last_backtrack_bytes;
     else if (n == "sw_second_pass") return h->swork.last_second_pass;
+    else if (n == "sw_instance") return h->swork.last_instance;
+    else if (n == "sw_instance_second") return h->swork.last_instance_second;
     else if (n == "sw_clock_mhz") return h->swork.last_clock_mhz;
     else if (n == "region_sw_all") own = h->swork.region_sw_all_calls;
     else if (n == "region_pick_timeouts") own = h->swork.region_pick_timeouts;

@@ -103,6 +103,8 @@ struct phmm_handle {
         hipEvent_t ev_second = nullptr;  // the one second pass of a call in pieces is done
         int lite_skip = 0;             // calls that go straight to the full Smith-Waterman instance (the last two-pass call met too many gaps)
         uint64_t last_second_pass = 0; // alignments of the last call that the full instance had to align again (phmm_get_stat "sw_second_pass")
+        uint64_t last_instance = 0;        // the kernel instance of the last call's first launch, and of the second pass that redid
+        uint64_t last_instance_second = 0; // alignments (0: none did): sw_pack_instance (phmm_get_stat "sw_instance", "sw_instance_second")
         unsigned char *ext = nullptr;  // bottom rows / strip edges of alignments too long for LDS (SwGeometry::ext_stride)
         size_t ext_bytes = 0;
         static constexpr int kMaxChunks = 8;      // pieces of one call: piece c+1 is staged and copied while piece c computes
@@ -264,6 +266,11 @@ struct SwGeometry {
     size_t strips = 0, lds_ref = 0, lds_alt = 0, lds_group = 0, gpb = 0, lds = 0, flag_words = 0, slab_stride = 0, max_workers = 0;
     size_t ext_stride = 0;  // > 0: the bottom row and strip edges of a block live in device memory (sequences beyond ~8 000 bases)
 };
+// A kernel instance as one integer (phmm_get_stat "sw_instance", include/phmm.h): K in bits 0-7, L in 8-15, transposed in 16,
+// the variant bits (phmm::SW_WIDE 1 | SW_EXT 2 | SW_LITE 4) in 17-19, the strip count in 32-63.
+inline uint64_t sw_pack_instance(int L, int K, bool transposed, int variant, size_t strips) {
+    return (uint64_t)(K & 0xff) | (uint64_t)(L & 0xff) << 8 | (uint64_t)transposed << 16 | (uint64_t)(variant & 7) << 17 | (uint64_t)strips << 32;
+}
 // (`params`: the weights decide between the scaled kernels and the wide instance, or refuse what overflows 32 bits in the
 // reference as well)
 int sw_plan(phmm_handle *h, const std::string &who, uint32_t n_alignments, uint32_t max_ref, uint32_t max_alt,

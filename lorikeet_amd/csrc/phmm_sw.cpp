@@ -443,6 +443,9 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     // (A second pass per piece costs a whole sweep's latency each, however few alignments it holds: a call in pieces takes two
     // passes on its own accord only where one second pass can serve all pieces -- below.)
     if (h->sw.sw_lite < 0 && !one_piece && (PJ ? false : on_device || max_slot > 64)) lite = false;
+    // (the decision is final here: what the first launch of this call is, for phmm_get_stat "sw_instance")
+    W.last_instance = phmm_host::sw_pack_instance(L, K, transposed, lite ? SW_LITE : G.variant, G.strips);
+    W.last_instance_second = 0;
     // A call in pieces whose results go to the caller takes ONE second pass behind its last piece: every piece's results are
     // fetched as soon as its first pass is done, and the few alignments the second pass redoes come back gathered (below).
     constexpr uint32_t kPatchMax = 4096;
@@ -866,6 +869,13 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         uint64_t again = 0;
         for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks); ++c) again += ((const uint32_t *)(W.host + o_st + 192))[c];
         W.last_second_pass = again;
+        // (a short list goes to the small-call instance, a longer one to the batch's own; per piece, or once behind the last piece)
+        uint64_t first_list = 0;
+        for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks) && !first_list; ++c) first_list = ((const uint32_t *)(W.host + o_st + 192))[c];
+        if (again)
+            W.last_instance_second = have_short && first_list <= kShortList
+                                         ? phmm_host::sw_pack_instance(GS.L, GS.K, GS.transposed, GS.variant, GS.strips)
+                                         : phmm_host::sw_pack_instance(L, K, transposed, G.variant, G.strips);
         if (again * 10 > (uint64_t)n_alignments * 3) W.lite_skip = 15;
     } else {
         W.last_second_pass = 0;

@@ -37,6 +37,24 @@ ALIGNMENT_TO_BEST_HAPLOTYPE_SW_PARAMETERS = Parameters(10, -15, -30, -5)
 
 _OPS = "MIDNSHP=X"
 
+SW_WIDE, SW_EXT, SW_LITE = 1, 2, 4  # variant bits of a kernel instance (phmm_sw_internal.hpp)
+
+
+def decode_instance(packed):
+    """phmm_get_stat "sw_instance" / "sw_instance_second" (include/phmm.h) -> dict(L, K, transposed, variant, wide, ext, lite,
+    strips), or None for 0 (no aligner call yet / no second pass)."""
+    packed = int(packed)
+    if packed == 0:
+        return None
+    variant = (packed >> 17) & 7
+    return {"L": (packed >> 8) & 0xff, "K": packed & 0xff, "transposed": bool((packed >> 16) & 1), "variant": variant,
+            "wide": bool(variant & SW_WIDE), "ext": bool(variant & SW_EXT), "lite": bool(variant & SW_LITE), "strips": packed >> 32}
+
+
+def last_instance(engine, second=False):
+    """The kernel instance the first launch (second=True: the second pass) of the engine's last aligner call was."""
+    return decode_instance(engine.stat("sw_instance_second" if second else "sw_instance"))
+
 
 class SmithWatermanAlignmentResult:
     """cigar: list of (length, op char); alignment_offset: int (smith_waterman_aligner.rs:454-476)."""

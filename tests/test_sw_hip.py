@@ -8,7 +8,7 @@ import pytest
 
 from lorikeet_amd import HipPairHMMEngine, PhmmError, _lib
 from lorikeet_amd.smith_waterman import (ALIGNMENT_TO_BEST_HAPLOTYPE_SW_PARAMETERS, NEW_SW_PARAMETERS, ORIGINAL_DEFAULT,
-                                         STANDARD_NGS, OverhangStrategy, Parameters, SmithWatermanAligner)
+                                         STANDARD_NGS, SW_EXT, OverhangStrategy, Parameters, SmithWatermanAligner, last_instance)
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +114,10 @@ def test_long_sequences_one_alignment_per_wave(aligner):
         g = aligner.align_batch([(big_ref, big_alt)], prm, strategy, capacity=4096)[0]
         _same(g, big_ref, big_alt, prm, strategy)
         assert len(g.elements) > 20
+        # ... by the one instance with its rows in device memory, <16, 32>, every strip of 512 columns of it
+        inst = last_instance(aligner.engine)
+        assert (inst["L"], inst["K"], inst["transposed"], inst["variant"]) == (16, 32, False, SW_EXT), inst
+        assert inst["strips"] == -(-len(big_alt) // 512)
     with pytest.raises(PhmmError, match="too long"):
         aligner.align(b"A" * 200000, b"C" * 1000, NEW_SW_PARAMETERS, "InDel")
 
