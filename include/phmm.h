@@ -647,6 +647,74 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
                           uint8_t *allele_flags, double *qual, uint32_t *flags, uint32_t *iterations);
 
 /*
+ * The annotation of called events: what the reference does with the read likelihoods once calculate_genotypes has returned
+ * a call -- the marginal onto the alleles of the call and VariantAnnotationEngine::annotate_context over it
+ * (src/haplotype/haplotype_caller_genotyping_engine.rs:330-393, :451-489; src/annotator/variant_annotator_engine.rs:32-113;
+ * src/annotator/variant_annotation.rs:93-405) -- for the events of many regions in ONE call, on the arrays
+ * phmm_genotype_likelihoods reads: the FORMAT fields AD, DP, AF, AC and the INFO fields DP, QD, MQ, BQ.  Per event e with
+ * C_e call alleles:
+ *   reads used      exactly phmm_genotype_likelihoods' rule (keep, read_sample, Locatable::overlaps with the widened window)
+ *   marginal        M[a][r] = max over the haplotypes of allele a, from -inf, then the rows of the call's alleles
+ *                   (AlleleLikelihoods::marginalize with the one-to-one subset of :376-384, allele_likelihoods.rs:633-740)
+ *   best allele     AlleleLikelihoods::search_best_allele with can_be_reference = true and the priorities 1 for the reference,
+ *                   0 otherwise (allele_likelihoods.rs:457-554, :1053-1095, assembly_based_caller_utils.rs:197-199): the first
+ *                   maximum, then among the alleles within 0.2 of it the highest priority, the second best looked up again;
+ *                   BestAllele::new's confidence (:1142-1160); informative iff confidence > 0.2 (:1163)
+ *   ad [s][c]       informative reads of sample s by best allele (DepthPerAlleleBySample, variant_annotation.rs:253-291); with
+ *                   C_e <= 1 the reference returns before it sets AD (:250-252): ad, af, ac, dp are 0 and flags has NO_AD
+ *   dp [s]          the sum of ad (:115-116);  ac [s]: alleles with ad > 0 (:162-171)
+ *   af [s][c]       ad / sum (MathUtils::normalize_sum_to_one, utils/math_utils.rs:402-415): a zero sum gives NaN as there
+ *   mq [c], bq [c]  over the informative reads of ALL samples with mapq != 0 (is_usable_read :356-358) by best allele: the element
+ *                   at index len / 2 of the sorted values (MathUtils::median, math_utils.rs:41-45), 30 when there are none
+ *                   (:188-236).  A read's BQ value is ReadUtils::get_read_base_quality_at_reference_coordinate at event_pos
+ *                   (src/reads/read_utils.rs:103-173): None outside [read_start, read_end] or before the soft start; the CIGAR
+ *                   walk from the soft start in which soft clips advance the reference position; None inside an element that
+ *                   consumes no read bases (D, N, H, P); a read that gives None adds nothing
+ *   info_dp         the sum of dp over the samples (GenotypesContext::get_dp, genotype/genotype_builder.rs:502-504)
+ *   qd_depth        get_depth (:360-405) over the called samples: the sum of dp where it is not 0, restricted to the samples
+ *                   with dp - ad[0] > 0 when there is one; a sample with dp == 0 (or NO_AD) counts its used reads + n_filtered
+ *                   (sample_evidence_count after add_evidence, haplotype_caller_genotyping_engine.rs:330-341)
+ *   qd              -10 log10_p_error / qd_depth (:317-318), the raw value; flags has QD_JITTER when it is not < 45.0: there the
+ *                   reference replaces it by 45 + 3 N(0, 1) from a thread RNG (fix_too_high_qd :416-424), which stays with the
+ *                   caller.  NO_QD (qd = 0) when the reference returns None: no log10_p_error, n_samples == 0, depth 0 (:302-315)
+ * Integers are exact and the doubles bit-equal to the reference's operations (no contraction); nothing depends on the order
+ * in which the device counts the reads.  PL subsetting, GT / GQ, reverse_trim_alleles, phasing and VCF output stay with the caller.
+ *   region_read_off ... event_hap_allele   as phmm_genotype_likelihoods
+ *   mapq [n_reads]     as phmm_region_compute takes it
+ *   call_allele_off [n_events+1], call_allele   the alleles of the call as indices into the event's alleles, strictly
+ *                      increasing, entry 0 being 0 (the reference); from phmm_allele_frequency's PHMM_AF_ALLELE_OUTPUT flags.
+ *                      An event with an empty list is not annotated: its dp, ac, info_dp, qd_depth, qd and flags are 0
+ *   read_off [n_reads+1], base_q   the qualities of each evidence read;  out_cigar_off [n_reads+1] / out_cigar / n_out_cigar
+ *                      its CIGAR as phmm_realign_reads returns it (BAM-encoded; the original one for a read left UNCHANGED);
+ *                      read_soft_start [n_reads] (get_soft_start); event_pos [n_events] = vc.loc.start.  These seven and bq are
+ *                      given together or are all NULL (BQ is then not computed)
+ *   sample_called [n_events x n_samples] or NULL (all)   0: the sample's genotype is a no-call (neither het, hom-var nor hom-ref)
+ *   log10_p_error [n_events]   the call's (phmm_allele_frequency's qual / -10); NaN (or the reference's 1.0): it has none
+ *   n_filtered [n_events x n_samples] or NULL (0)   reads of per_sample_filtered_read_list that overlap the window
+ *   ad, af             n_samples x C_e values, sample-major [s][c], at n_samples * call_allele_off[e];  mq, bq: C_e at call_allele_off[e]
+ *   dp, ac [n_events x n_samples];  info_dp, qd_depth, qd, flags [n_events]
+ * Limits: A_e <= 1 024 (what phmm_genotype_likelihoods admits at ploidy 1); ploidy and the genotype count play no part here.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offending event or read): a required array NULL,
+ * offsets not monotonic, A_e == 0 or > 1 024, a map entry < -1 or >= A_e, event_region >= n_regions, read_sample >= n_samples,
+ * call_allele[0] != 0, a call allele >= A_e or not increasing, the BQ arrays given in part, n_out_cigar beyond its slot.
+ * n_events == 0 returns PHMM_OK.  One thread per handle.
+ */
+#define PHMM_ANN_NO_AD 1u
+#define PHMM_ANN_NO_QD 2u
+#define PHMM_ANN_QD_JITTER 4u
+int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *region_read_off, const uint32_t *region_hap_off,
+                         const uint64_t *out_off, const double *likelihoods, const uint8_t *keep, const uint32_t *read_sample,
+                         const int64_t *read_start, const int64_t *read_end, const uint8_t *mapq, uint32_t n_samples,
+                         uint32_t n_events, const uint32_t *event_region, const uint32_t *event_allele_off,
+                         const int64_t *event_start, const int64_t *event_end, const int32_t *event_hap_allele,
+                         const uint32_t *call_allele_off, const uint32_t *call_allele, const uint32_t *read_off,
+                         const uint8_t *base_q, const uint64_t *out_cigar_off, const uint32_t *out_cigar,
+                         const uint32_t *n_out_cigar, const int64_t *read_soft_start, const int64_t *event_pos,
+                         const uint8_t *sample_called, const double *log10_p_error, const uint32_t *n_filtered, int32_t *ad,
+                         int32_t *dp, double *af, uint32_t *ac, uint8_t *mq, uint8_t *bq, int32_t *info_dp, int32_t *qd_depth,
+                         double *qd, uint32_t *flags);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):

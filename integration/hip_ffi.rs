@@ -85,6 +85,10 @@ pub const PHMM_AF_TOO_MANY_ALLELES: c_uint = 8;
 pub const PHMM_AF_NOT_CONVERGED: c_uint = 16;
 pub const PHMM_AF_ALLELE_PLAUSIBLE: c_uint = 1;
 pub const PHMM_AF_ALLELE_OUTPUT: c_uint = 2;
+/// `phmm_annotate_events`: per-event flags
+pub const PHMM_ANN_NO_AD: c_uint = 1;
+pub const PHMM_ANN_NO_QD: c_uint = 2;
+pub const PHMM_ANN_QD_JITTER: c_uint = 4;
 
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
 /// (src/reads/alignment_utils.rs:52-58, src/model/allele_likelihoods.rs:17)
@@ -614,6 +618,50 @@ extern "C" {
         qual: *mut f64,
         flags: *mut u32,
         iterations: *mut u32,
+    ) -> c_int;
+    /// the marginal onto the alleles of the call and VariantAnnotationEngine::annotate_context over it
+    /// (haplotype_caller_genotyping_engine.rs:330-393, variant_annotation.rs:93-405): AD, DP, AF, AC per sample, DP, QD, MQ, BQ per event
+    pub fn phmm_annotate_events(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_read_off: *const u32,
+        region_hap_off: *const u32,
+        out_off: *const u64,
+        likelihoods: *const f64,
+        keep: *const u8,
+        read_sample: *const u32,
+        read_start: *const i64,
+        read_end: *const i64,
+        mapq: *const u8,
+        n_samples: u32,
+        n_events: u32,
+        event_region: *const u32,
+        event_allele_off: *const u32,
+        event_start: *const i64,
+        event_end: *const i64,
+        event_hap_allele: *const i32,
+        call_allele_off: *const u32,
+        call_allele: *const u32,
+        read_off: *const u32,
+        base_q: *const u8,
+        out_cigar_off: *const u64,
+        out_cigar: *const u32,
+        n_out_cigar: *const u32,
+        read_soft_start: *const i64,
+        event_pos: *const i64,
+        sample_called: *const u8,
+        log10_p_error: *const f64,
+        n_filtered: *const u32,
+        ad: *mut i32,
+        dp: *mut i32,
+        af: *mut f64,
+        ac: *mut u32,
+        mq: *mut u8,
+        bq: *mut u8,
+        info_dp: *mut i32,
+        qd_depth: *mut i32,
+        qd: *mut f64,
+        flags: *mut u32,
     ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;

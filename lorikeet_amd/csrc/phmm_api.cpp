@@ -400,6 +400,8 @@ void phmm_destroy(phmm_handle *h) {
     if (h->gwork.d_jacobian) (void)hipFree(h->gwork.d_jacobian);
     if (h->afwork.dev) (void)hipFree(h->afwork.dev);
     if (h->afwork.host) (void)hipHostFree(h->afwork.host);
+    if (h->annwork.dev) (void)hipFree(h->annwork.dev);
+    if (h->annwork.host) (void)hipHostFree(h->annwork.host);
     for (int c = 0; c < phmm_handle::SwWork::kMaxChunks; ++c)
         for (hipEvent_t e : {h->swork.ev_in[c], h->swork.ev_out[c], h->swork.ev_k0[c], h->swork.ev_k1[c]})
             if (e) (void)hipEventDestroy(e);

@@ -137,6 +137,10 @@ struct phmm_handle {
         char *dev = nullptr, *host = nullptr;
         size_t cap = 0;
     } afwork;
+    struct AnnWork {  // phmm_annotate_events (phmm_annotate.cpp): grow-only staging
+        char *dev = nullptr, *host = nullptr;
+        size_t cap = 0;
+    } annwork;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

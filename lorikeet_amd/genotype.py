@@ -159,3 +159,81 @@ def allele_frequency(engine, pl, pl_off=None, allele_off=None, allele_length=Non
     if code != _lib.PHMM_OK:
         raise PhmmError(code, engine.last_error())
     return AFResult(ao, pnv, pvp, absent, mle, aflags, qual, flags, iters)
+
+
+# ---- the annotation of called events (phmm_annotate_events) ----------------------------------------------------------------
+
+class AlignedReads:
+    """What BQ reads of each evidence read (all reads of the batch, in order): read_off [n_reads + 1] into base_q, the read's
+    CIGAR after realignment (BAM-encoded elements; `cigars`: one array per read), its soft start, and per event its position
+    (vc.loc.start)."""
+
+    def __init__(self, read_off, base_q, cigars, soft_start, event_pos):
+        self.read_off = np.ascontiguousarray(read_off, np.uint32)
+        self.base_q = np.ascontiguousarray(base_q, np.uint8)
+        cigars = [np.ascontiguousarray(c, np.uint32) for c in cigars]
+        self.n_cigar = np.array([len(c) for c in cigars], np.uint32)
+        self.cigar_off = np.concatenate([[0], np.cumsum(self.n_cigar)]).astype(np.uint64)
+        self.cigar = np.concatenate(cigars).astype(np.uint32) if cigars else np.zeros(0, np.uint32)
+        if not len(self.cigar):
+            self.cigar = np.zeros(1, np.uint32)
+        self.soft_start = np.ascontiguousarray(soft_start, np.int64)
+        self.event_pos = np.ascontiguousarray(event_pos, np.int64)
+
+
+class AnnotationResult:
+    """Per event e: ad[e] / af[e] as [n_samples, C_e] arrays, mq[e] / bq[e] over its call alleles (bq None without the BQ
+    inputs); dp / ac as [n_events, n_samples]; info_dp, qd_depth, qd, flags (PHMM_ANN_*) per event."""
+
+    def __init__(self, ad, af, dp, ac, mq, bq, info_dp, qd_depth, qd, flags):
+        self.ad, self.af, self.dp, self.ac, self.mq, self.bq = ad, af, dp, ac, mq, bq
+        self.info_dp, self.qd_depth, self.qd, self.flags = info_dp, qd_depth, qd, flags
+
+
+def call_alleles_of(af_result):
+    """The alleles of each call from an AFResult: the reference and every allele with PHMM_AF_ALLELE_OUTPUT, for the events
+    that are CALLED; an empty list otherwise."""
+    return [[0] + [a for a in range(1, len(fl)) if fl[a] & _lib.PHMM_AF_ALLELE_OUTPUT] if af_result.called(e) else []
+            for e, fl in enumerate(af_result.allele_flags)]
+
+
+def annotate_events(engine, batch, likelihoods, keep, read_start, read_end_, read_sample, mapq, events, call_alleles,
+                    log10_p_error, n_samples=1, aligned=None, sample_called=None, n_filtered=None):
+    """AD, DP, AF, AC per sample and DP, QD, MQ, BQ per event for a batch of called events (phmm_annotate_events,
+    include/phmm.h).  The region / read / event arguments are genotype_likelihoods'; mapq: per read; call_alleles: per event
+    the indices of the call's alleles among the event's (reference first; empty: not annotated; call_alleles_of);
+    log10_p_error: per event (NaN: none); aligned: AlignedReads or None (no BQ); sample_called / n_filtered:
+    [n_events, n_samples] or None."""
+    lk = np.ascontiguousarray(likelihoods, np.float64)
+    kp = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    rs, re_ = np.ascontiguousarray(read_start, np.int64), np.ascontiguousarray(read_end_, np.int64)
+    smp, mq_in = np.ascontiguousarray(read_sample, np.uint32), np.ascontiguousarray(mapq, np.uint8)
+    n_ev, S = events.n_events, int(n_samples)
+    C = np.array([len(c) for c in call_alleles], np.int64)
+    c_off = np.concatenate([[0], np.cumsum(C)]).astype(np.uint32)
+    ca = np.array([a for c in call_alleles for a in c] + ([] if int(c_off[-1]) else [0]), np.uint32)
+    err = np.ascontiguousarray(log10_p_error, np.float64)
+    sc = None if sample_called is None else np.ascontiguousarray(sample_called, np.uint8).reshape(-1)
+    nf = None if n_filtered is None else np.ascontiguousarray(n_filtered, np.uint32).reshape(-1)
+    n_call = int(c_off[-1])
+    ad, af = np.zeros(n_call * S, np.int32), np.zeros(n_call * S)
+    dp, ac = np.zeros(n_ev * S, np.int32), np.zeros(n_ev * S, np.uint32)
+    mq, bq = np.zeros(n_call, np.uint8), None if aligned is None else np.zeros(n_call, np.uint8)
+    info_dp, qd_depth, qd, flags = np.zeros(n_ev, np.int32), np.zeros(n_ev, np.int32), np.zeros(n_ev), np.zeros(n_ev, np.uint32)
+    al = aligned
+    code = engine.lib.phmm_annotate_events(
+        engine._h, batch.n_regions, _p(batch.region_read_off, _lib.u32p), _p(batch.region_hap_off, _lib.u32p), _p(batch.out_off, _lib.u64p),
+        _p(lk, _lib.f64p), _p(kp, _lib.u8p), _p(smp, _lib.u32p), _p(rs, _i64p), _p(re_, _i64p), _p(mq_in, _lib.u8p), S, n_ev,
+        _p(events.region, _lib.u32p), _p(events.allele_off, _lib.u32p), _p(events.start, _i64p), _p(events.end, _i64p),
+        _p(events.hap_allele, _i32p), _p(c_off, _lib.u32p), _p(ca, _lib.u32p),
+        _p(al and al.read_off, _lib.u32p), _p(al and al.base_q, _lib.u8p), _p(al and al.cigar_off, _lib.u64p), _p(al and al.cigar, _lib.u32p),
+        _p(al and al.n_cigar, _lib.u32p), _p(al and al.soft_start, _i64p), _p(al and al.event_pos, _i64p),
+        _p(sc, _lib.u8p), _p(err, _lib.f64p), _p(nf, _lib.u32p), _p(ad, _i32p), _p(dp, _i32p), _p(af, _lib.f64p), _p(ac, _lib.u32p),
+        _p(mq, _lib.u8p), _p(bq, _lib.u8p), _p(info_dp, _i32p), _p(qd_depth, _i32p), _p(qd, _lib.f64p), _p(flags, _lib.u32p))
+    if code != _lib.PHMM_OK:
+        raise PhmmError(code, engine.last_error())
+    lo = lambda e: int(c_off[e])  # noqa: E731
+    per_sample = lambda a: [a[S * lo(e):S * lo(e + 1)].reshape(S, int(C[e])) for e in range(n_ev)]  # noqa: E731
+    per_allele = lambda a: None if a is None else [a[lo(e):lo(e + 1)] for e in range(n_ev)]  # noqa: E731
+    return AnnotationResult(per_sample(ad), per_sample(af), dp.reshape(n_ev, S), ac.reshape(n_ev, S), per_allele(mq), per_allele(bq),
+                            info_dp, qd_depth, qd, flags)

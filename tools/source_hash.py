@@ -13,7 +13,8 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "sw": ("phmm_sw_internal.hpp", "phmm_sw_kernels.hip", "phmm_sw_device.hpp"),
     "cigar": ("phmm_cigar_internal.hpp", "phmm_cigar_kernels.hip", "phmm_cigar_device.hpp"),
     "server": ("phmm_server.hpp", "phmm_server_kernels.hip"),
-    "genotype": ("phmm_genotype_internal.hpp", "phmm_genotype_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip"),
+    "genotype": ("phmm_genotype_internal.hpp", "phmm_genotype_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip",
+                 "phmm_annotate_internal.hpp", "phmm_annotate_kernels.hip"),
 }
 
 
