@@ -647,6 +647,75 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
                           uint8_t *allele_flags, double *qual, uint32_t *flags, uint32_t *iterations);
 
 /*
+ * Genotype assignment per event and sample: what GenotypingEngine::calculate_genotypes does with the PLs once the output
+ * alleles are known (src/genotype/genotyping_engine.rs:199-235), for many events in ONE call, on the PL layout
+ * phmm_genotype_likelihoods writes and phmm_allele_frequency reads -- the FORMAT fields PL, GT, GQ (and GP, PG) of the call,
+ * and the sample_called argument of phmm_annotate_events, so the three calls chain without a host step.  Per event e with
+ * C_e call alleles and G'_e = phmm_genotype_count(ploidy, C_e):
+ *   index table     AlleleSubsettingUtils::subsetted_pl_indices (src/model/allele_subsetting_utils.rs:310-353): the genotype of
+ *                   the call with index g' keeps its allele counts, its alleles become the event's, its index there is the old one
+ *   likelihoods     pl / -10.0 of the kept genotypes (Genotype::get_likelihoods -> pls_to_gls, genotype_likelihoods.rs:80-85),
+ *                   not scaled: the result of scale_log_space_array_for_numeric_stability is discarded there (:214)
+ *   sub_pl          gls_to_pls of them (genotype_likelihoods.rs:55-78; depth = vc.get_dp(), emit_empty_pls = true: always set)
+ *   PHMM_GT_USE_PLS (UsePLsToAssign, the reference's default; make_genotype_call, src/model/variant_context.rs:309-361)
+ *                   is_informative (:573-575): the sum of the likelihoods in index order < SUM_GL_THRESH_NOCALL = -0.1 (:109);
+ *                   if not, GT is a no-call and GQ none (UNINFORMATIVE).  Otherwise the genotype is the first maximum
+ *                   (MathUtils::max_element_index, src/utils/math_utils.rs:141-150), GQ = (log10 * -10.0).round() as i32
+ *                   (genotype_builder.rs:220-222) of get_gq_log10_from_likelihoods (genotype_likelihoods.rs:87-109: the chosen
+ *                   minus the largest other, a `>=` scan; its normalising arm needs a negative difference, which the first
+ *                   maximum never gives).  A best genotype with <NON_REF> in it: GT no-call, sub_pl all 0, GQ kept (NON_REF_BEST)
+ *   PHMM_GT_USE_POSTERIORS (UsePosteriorProbabilities, :380-438)   the priors of GenotypePriorCalculator::assuming_hw(
+ *                   log10_snp_het, log10_indel_het, None).get_log10_priors (src/genotype/genotype_prior_calculator.rs:116-229;
+ *                   allele types by length against the reference's, '*' included), posteriors = priors + likelihoods, scaled by
+ *                   their maximum; pg = priors * -10, gp = scaled posteriors * -10 (== 0.0 -> 0.0); GT the first maximum, never a
+ *                   no-call; GQ from get_gq_log10_from_posteriors (:524-571) in its 0/1, 2, 3 and general arms
+ *   log10_p_error_posterior   the QUAL update of --use-posteriors-to-calculate-qual (genotyping_engine.rs:216-235):
+ *                   phred_no_variant_posterior_probability (:252-269) over extract_p_no_alt_with_posteriors (:282-326, with a '*'
+ *                   in the call it reads posteriors[n] for n in 0..ploidy as written there), times -0.1, through
+ *                   log10_one_minus_pow10 when site_monomorphic; NaN where the reference makes no update
+ *   type            GenotypeBuilder::determine_type (src/genotype/genotype_builder.rs:399-441); sample_called = 1 iff Het, HomVar
+ *                   or HomRef, the predicate of get_depth (src/annotator/variant_annotation.rs:369)
+ *   C_e == 1        VariantContext::subset_to_ref_only (variant_context.rs:586-619): GT all 0, no PLs, GQ none, called (REF_ONLY)
+ * The AD arm of subset_alleles (:274-291) is dead at this call site (the genotypes come from build_from_likelihoods and have
+ * no AD): AD stays phmm_annotate_events'.  The other four assignment methods -- SetToNoCall, SetToNoCallNoAnnotations,
+ * BestMatchToOriginal (the original GT is empty here) and DoNotAssignGenotypes -- compute nothing and stay with the caller.
+ * The default method is bit-equal to the reference's operations.  The posterior method's exp10 / log10 are the device's (ocml)
+ * and its log10_sum_log10 adds in a fixed order of its own: about 1e-13 relative, bit-identical from run to run and whatever the batch.
+ *   event_allele_off, pl_off, pl    as phmm_allele_frequency
+ *   allele_length [off[n]] or NULL  Allele::length(); required by the posterior method
+ *   allele_kind [off[n]] or NULL    PHMM_AF_KIND_*: recognises <NON_REF> (default method) and '*' (the QUAL update); NULL: all plain
+ *   call_allele_off [n_events+1], call_allele   as phmm_annotate_events: strictly increasing, entry 0 is 0; an event with an
+ *                                   empty list is not called: nothing of it is read and its outputs are 0
+ *   method                          PHMM_GT_USE_PLS or PHMM_GT_USE_POSTERIORS
+ *   log10_snp_het, log10_indel_het  assuming_hw's arguments (log10 of --snp-heterozygosity / --indel-heterozygosity); posterior method
+ *   site_monomorphic [n_events] or NULL (0)   PHMM_AF_MONOMORPHIC of phmm_allele_frequency's flags; posterior method
+ *   sub_pl_off [n_events+1]         event e writes n_samples x G'_e values, sample-major [s][g'], at sub_pl / gp / pg +
+ *                                   sub_pl_off[e]; nothing with C_e <= 1
+ *   gt [n_events x n_samples x ploidy]   indices into the event's call_allele list (0 = the reference), non-decreasing
+ *                                   (GenotypeAlleleCounts::as_allele_list); -1: a no-call allele
+ *   gq [n_events x n_samples]       -1: none;  log10_gq (or NULL): the value before rounding, NaN where GQ is none
+ *   sample_called [n_events x n_samples]   phmm_annotate_events' argument
+ *   sample_flags [n_events x n_samples]    PHMM_GT_SAMPLE_*
+ *   gp, pg, log10_p_error_posterior [n_events]   posterior method only; NULL (and untouched) otherwise
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offending event): a required array NULL, offsets not
+ * monotonic, ploidy 0, A_e < 2, an unknown method, and for an event with a call: G_e > 1 024, call_allele[0] != 0, a call allele
+ * >= A_e or not increasing, an unknown kind, a pl_off or sub_pl_off slot too small, <NON_REF> in the call with the posterior
+ * method (the reference panics there: calculate_allele_types).  n_events == 0 returns PHMM_OK.  One thread per handle.
+ */
+#define PHMM_GT_USE_PLS 0u
+#define PHMM_GT_USE_POSTERIORS 1u
+#define PHMM_GT_SAMPLE_UNINFORMATIVE 1u
+#define PHMM_GT_SAMPLE_NON_REF_BEST 2u
+#define PHMM_GT_SAMPLE_REF_ONLY 4u
+int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples, uint32_t ploidy,
+                          const uint32_t *event_allele_off, const uint32_t *allele_length, const uint8_t *allele_kind,
+                          const uint64_t *pl_off, const int32_t *pl, const uint32_t *call_allele_off,
+                          const uint32_t *call_allele, uint32_t method, double log10_snp_het, double log10_indel_het,
+                          const uint8_t *site_monomorphic, const uint64_t *sub_pl_off, int32_t *sub_pl, int32_t *gt,
+                          int32_t *gq, double *log10_gq, uint8_t *sample_called, uint8_t *sample_flags, double *gp, double *pg,
+                          double *log10_p_error_posterior);
+
+/*
  * The annotation of called events: what the reference does with the read likelihoods once calculate_genotypes has returned
  * a call -- the marginal onto the alleles of the call and VariantAnnotationEngine::annotate_context over it
  * (src/haplotype/haplotype_caller_genotyping_engine.rs:330-393, :451-489; src/annotator/variant_annotator_engine.rs:32-113;
@@ -678,7 +747,8 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
  *                   reference replaces it by 45 + 3 N(0, 1) from a thread RNG (fix_too_high_qd :416-424), which stays with the
  *                   caller.  NO_QD (qd = 0) when the reference returns None: no log10_p_error, n_samples == 0, depth 0 (:302-315)
  * Integers are exact and the doubles bit-equal to the reference's operations (no contraction); nothing depends on the order
- * in which the device counts the reads.  PL subsetting, GT / GQ, reverse_trim_alleles, phasing and VCF output stay with the caller.
+ * in which the device counts the reads.  PL subsetting and GT / GQ are phmm_assign_genotypes above (its sample_called goes in
+ * here as it is); reverse_trim_alleles, phasing, fix_too_high_qd's draw and VCF output stay with the caller.
  *   region_read_off ... event_hap_allele   as phmm_genotype_likelihoods
  *   mapq [n_reads]     as phmm_region_compute takes it
  *   call_allele_off [n_events+1], call_allele   the alleles of the call as indices into the event's alleles, strictly

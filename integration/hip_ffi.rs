@@ -85,6 +85,12 @@ pub const PHMM_AF_TOO_MANY_ALLELES: c_uint = 8;
 pub const PHMM_AF_NOT_CONVERGED: c_uint = 16;
 pub const PHMM_AF_ALLELE_PLAUSIBLE: c_uint = 1;
 pub const PHMM_AF_ALLELE_OUTPUT: c_uint = 2;
+/// `phmm_assign_genotypes`: assignment methods, per-sample flags
+pub const PHMM_GT_USE_PLS: c_uint = 0;
+pub const PHMM_GT_USE_POSTERIORS: c_uint = 1;
+pub const PHMM_GT_SAMPLE_UNINFORMATIVE: c_uint = 1;
+pub const PHMM_GT_SAMPLE_NON_REF_BEST: c_uint = 2;
+pub const PHMM_GT_SAMPLE_REF_ONLY: c_uint = 4;
 /// `phmm_annotate_events`: per-event flags
 pub const PHMM_ANN_NO_AD: c_uint = 1;
 pub const PHMM_ANN_NO_QD: c_uint = 2;
@@ -618,6 +624,36 @@ extern "C" {
         qual: *mut f64,
         flags: *mut u32,
         iterations: *mut u32,
+    ) -> c_int;
+    /// AlleleSubsettingUtils::subset_alleles and VariantContext::make_genotype_call per event and sample
+    /// (genotyping_engine.rs:199-235): the subsetted PLs, GT, GQ, the sample_called flags of phmm_annotate_events, and with
+    /// the posterior method GP, PG and the QUAL update
+    pub fn phmm_assign_genotypes(
+        h: *mut phmm_handle,
+        n_events: u32,
+        n_samples: u32,
+        ploidy: u32,
+        event_allele_off: *const u32,
+        allele_length: *const u32,
+        allele_kind: *const u8,
+        pl_off: *const u64,
+        pl: *const i32,
+        call_allele_off: *const u32,
+        call_allele: *const u32,
+        method: u32,
+        log10_snp_het: f64,
+        log10_indel_het: f64,
+        site_monomorphic: *const u8,
+        sub_pl_off: *const u64,
+        sub_pl: *mut i32,
+        gt: *mut i32,
+        gq: *mut i32,
+        log10_gq: *mut f64,
+        sample_called: *mut u8,
+        sample_flags: *mut u8,
+        gp: *mut f64,
+        pg: *mut f64,
+        log10_p_error_posterior: *mut f64,
     ) -> c_int;
     /// the marginal onto the alleles of the call and VariantAnnotationEngine::annotate_context over it
     /// (haplotype_caller_genotyping_engine.rs:330-393, variant_annotation.rs:93-405): AD, DP, AF, AC per sample, DP, QD, MQ, BQ per event

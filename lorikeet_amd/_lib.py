@@ -33,6 +33,8 @@ PHMM_REGION_SKIP_SINGLE_ALLELE = 1
 PHMM_AF_KIND_PLAIN, PHMM_AF_KIND_SPAN_DEL, PHMM_AF_KIND_NON_REF = 0, 1, 2
 PHMM_AF_CALLED, PHMM_AF_LOW_QUAL, PHMM_AF_MONOMORPHIC, PHMM_AF_TOO_MANY_ALLELES, PHMM_AF_NOT_CONVERGED = 1, 2, 4, 8, 16
 PHMM_AF_ALLELE_PLAUSIBLE, PHMM_AF_ALLELE_OUTPUT = 1, 2
+PHMM_GT_USE_PLS, PHMM_GT_USE_POSTERIORS = 0, 1
+PHMM_GT_SAMPLE_UNINFORMATIVE, PHMM_GT_SAMPLE_NON_REF_BEST, PHMM_GT_SAMPLE_REF_ONLY = 1, 2, 4
 PHMM_ANN_NO_AD, PHMM_ANN_NO_QD, PHMM_ANN_QD_JITTER = 1, 2, 4
 
 class EngineConfig(C.Structure):
@@ -129,6 +131,9 @@ SYMBOLS = [
     ("phmm_allele_frequency", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u8p, u64p, C.POINTER(C.c_int32),
                                         C.c_double, C.c_double, C.c_double, C.c_double, f64p, f64p, f64p, C.POINTER(C.c_int64), u8p,
                                         f64p, u32p, u32p]),
+    ("phmm_assign_genotypes", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u8p, u64p, C.POINTER(C.c_int32),
+                                        u32p, u32p, C.c_uint32, C.c_double, C.c_double, u8p, u64p, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), f64p, u8p, u8p, f64p, f64p, f64p]),
     ("phmm_annotate_events", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u64p, f64p, u8p, u32p, C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), u8p, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u64p, u32p, u32p,

@@ -402,6 +402,8 @@ void phmm_destroy(phmm_handle *h) {
     if (h->afwork.host) (void)hipHostFree(h->afwork.host);
     if (h->annwork.dev) (void)hipFree(h->annwork.dev);
     if (h->annwork.host) (void)hipHostFree(h->annwork.host);
+    if (h->aswork.dev) (void)hipFree(h->aswork.dev);
+    if (h->aswork.host) (void)hipHostFree(h->aswork.host);
     for (int c = 0; c < phmm_handle::SwWork::kMaxChunks; ++c)
         for (hipEvent_t e : {h->swork.ev_in[c], h->swork.ev_out[c], h->swork.ev_k0[c], h->swork.ev_k1[c]})
             if (e) (void)hipEventDestroy(e);

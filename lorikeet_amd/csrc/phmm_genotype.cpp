@@ -41,21 +41,11 @@ int fail(phmm_handle *h, const std::string &msg) {
 
 constexpr uint32_t kMaxPloidy = 65535;  // (a genotype's allele counts are 16-bit in the kernel's table)
 
-// GenotypeLikelihoodCalculators::build_allele_first_genotype_offset_table (genotype_likelihood_calculators.rs:180-200),
-// saturating instead of the reference's -1 on overflow: off[p][a] = genotypes of ploidy p whose alleles are all below a
-std::vector<std::vector<uint64_t>> offset_table(uint32_t ploidy, uint32_t n_alleles) {
-    std::vector<std::vector<uint64_t>> off(ploidy + 1, std::vector<uint64_t>(n_alleles + 1, 0));
-    for (uint32_t a = 1; a <= n_alleles; ++a) off[0][a] = 1;
-    for (uint32_t p = 1; p <= ploidy; ++p)
-        for (uint32_t a = 1; a <= n_alleles; ++a) off[p][a] = std::min<uint64_t>(off[p][a - 1] + off[p - 1][a], UINT32_MAX);
-    return off;
-}
-
 // The genotypes of (ploidy, n_alleles) in the reference's index order (allele_heap_to_index, genotype_likelihood_calculator.rs:
 // 273-295: the sorted alleles a_1 <= ... <= a_p sit at sum offset[i][a_i]); each as its distinct alleles, ascending, with
 // their counts (GenotypeAlleleCounts).  Only called with genotype_count(ploidy, n_alleles) <= GT_MAX_GENOTYPES.
 void genotype_table(uint32_t ploidy, uint32_t n_alleles, std::vector<uint32_t> *comp_off, std::vector<uint32_t> *comp) {
-    const auto off = offset_table(ploidy, n_alleles);
+    const auto off = genotype_offset_table(ploidy, n_alleles);
     const uint32_t G = (uint32_t)off[ploidy][n_alleles];
     std::vector<std::vector<uint32_t>> by_index(G);
     std::vector<uint32_t> counts(n_alleles, 0);
@@ -88,6 +78,14 @@ void genotype_table(uint32_t ploidy, uint32_t n_alleles, std::vector<uint32_t> *
 }
 
 }  // namespace
+
+std::vector<std::vector<uint64_t>> genotype_offset_table(uint32_t ploidy, uint32_t n_alleles) {
+    std::vector<std::vector<uint64_t>> off(ploidy + 1, std::vector<uint64_t>(n_alleles + 1, 0));
+    for (uint32_t a = 1; a <= n_alleles; ++a) off[0][a] = 1;
+    for (uint32_t p = 1; p <= ploidy; ++p)
+        for (uint32_t a = 1; a <= n_alleles; ++a) off[p][a] = std::min<uint64_t>(off[p][a - 1] + off[p - 1][a], UINT32_MAX);
+    return off;
+}
 
 const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &genotype_table_of(phmm_handle *h, uint32_t ploidy, uint32_t n_alleles) {
     auto &T = h->gwork.tables[(uint64_t)ploidy << 32 | n_alleles];

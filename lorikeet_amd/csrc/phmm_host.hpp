@@ -141,6 +141,10 @@ struct phmm_handle {
         char *dev = nullptr, *host = nullptr;
         size_t cap = 0;
     } annwork;
+    struct AsWork {  // phmm_assign_genotypes (phmm_assign.cpp): grow-only staging
+        char *dev = nullptr, *host = nullptr;
+        size_t cap = 0;
+    } aswork;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit
@@ -155,6 +159,11 @@ struct phmm_handle {
 // use; phmm_genotype.cpp): [G + 1] component offsets, components (allele | count << 16) with the alleles ascending.  Only for
 // phmm_genotype_count(ploidy, n_alleles) <= 1 024.
 const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &genotype_table_of(phmm_handle *h, uint32_t ploidy, uint32_t n_alleles);
+
+// GenotypeLikelihoodCalculators::build_allele_first_genotype_offset_table (genotype_likelihood_calculators.rs:180-200),
+// saturating at UINT32_MAX instead of the reference's -1 on overflow: off[p][a] = genotypes of ploidy p whose alleles are all
+// below a.  The index of the sorted alleles a_1 <= ... <= a_p is the sum of off[i][a_i] (phmm_genotype.cpp).
+std::vector<std::vector<uint64_t>> genotype_offset_table(uint32_t ploidy, uint32_t n_alleles);
 
 namespace phmm_host {
 

@@ -161,6 +161,71 @@ def allele_frequency(engine, pl, pl_off=None, allele_off=None, allele_length=Non
     return AFResult(ao, pnv, pvp, absent, mle, aflags, qual, flags, iters)
 
 
+# ---- genotype assignment (phmm_assign_genotypes) ---------------------------------------------------------------------------
+
+class AssignResult:
+    """Per event e: sub_pl[e] as an [n_samples, G'_e] array over the genotypes of the call's alleles (gp[e] / pg[e] alike with
+    the posterior method, else None); gt as [n_events, n_samples, ploidy] indices into the call's alleles (-1: no call); gq
+    (-1: none), log10_gq, sample_called, sample_flags (PHMM_GT_SAMPLE_*) as [n_events, n_samples];
+    log10_p_error_posterior per event (posterior method; NaN: no update) or None; call_alleles as given."""
+
+    def __init__(self, call_alleles, sub_pl, gt, gq, log10_gq, sample_called, sample_flags, gp, pg, log10_p_error_posterior):
+        self.call_alleles, self.sub_pl, self.gt, self.gq, self.log10_gq = call_alleles, sub_pl, gt, gq, log10_gq
+        self.sample_called, self.sample_flags, self.gp, self.pg = sample_called, sample_flags, gp, pg
+        self.log10_p_error_posterior = log10_p_error_posterior
+
+
+def assign_genotypes(engine, af_or_call_alleles, pl, allele_off, pl_off=None, allele_length=None, allele_kind=None,
+                     n_samples=1, ploidy=2, method=_lib.PHMM_GT_USE_PLS, log10_snp_het=-3.0, log10_indel_het=np.log10(1.25e-4),
+                     site_monomorphic=None):
+    """PL subsetting, GT and GQ per sample for a batch of events (phmm_assign_genotypes, include/phmm.h).
+    af_or_call_alleles: an AFResult of allele_frequency (the call's alleles and site_monomorphic then come from it) or per
+    event the indices of the call's alleles (reference first; empty: not called); pl / pl_off / allele_length / allele_kind: as
+    allele_frequency takes them (pl_off comes from a GenotypeResult, else it is required); allele_off [n_events + 1]; log10_snp_het / log10_indel_het: log10 of --snp-heterozygosity and
+    --indel-heterozygosity (defaults: src/cli.rs:1509-1520), the posterior method's."""
+    if isinstance(af_or_call_alleles, AFResult):
+        call_alleles = call_alleles_of(af_or_call_alleles)
+        if site_monomorphic is None:
+            site_monomorphic = (np.asarray(af_or_call_alleles.flags) & _lib.PHMM_AF_MONOMORPHIC) != 0
+    else:
+        call_alleles = [list(c) for c in af_or_call_alleles]
+    if isinstance(pl, GenotypeResult):
+        n_samples = np.shape(pl.pl[0])[0] if pl.pl else n_samples
+        parts = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in pl.pl]
+        pl_off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.uint64)
+        pl = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    if pl_off is None:
+        raise ValueError("assign_genotypes: pl_off is required unless pl is a GenotypeResult")
+    pl = np.ascontiguousarray(pl, np.int32)
+    pl_off = np.ascontiguousarray(pl_off, np.uint64)
+    ao = np.ascontiguousarray(allele_off, np.uint32)
+    ln = None if allele_length is None else np.ascontiguousarray(allele_length, np.uint32)
+    kd = None if allele_kind is None else np.ascontiguousarray(allele_kind, np.uint8)
+    mono = None if site_monomorphic is None else np.ascontiguousarray(site_monomorphic, np.uint8)
+    n_ev, S, P = len(ao) - 1, int(n_samples), int(ploidy)
+    C = np.array([len(c) for c in call_alleles], np.int64)
+    c_off = np.concatenate([[0], np.cumsum(C)]).astype(np.uint32)
+    ca = np.array([a for c in call_alleles for a in c] + ([] if int(c_off[-1]) else [0]), np.uint32)
+    Gn = np.array([genotype_count(P, int(c)) if c >= 2 else 0 for c in C], np.uint64)
+    s_off = np.concatenate([[0], np.cumsum(Gn * np.uint64(S))]).astype(np.uint64)
+    n_sub = max(int(s_off[-1]), 1)
+    posterior = int(method) == _lib.PHMM_GT_USE_POSTERIORS
+    sub_pl, gt = np.zeros(n_sub, np.int32), np.zeros(max(n_ev * S * P, 1), np.int32)
+    gq, log10_gq = np.zeros(n_ev * S, np.int32), np.zeros(n_ev * S)
+    called, sflags = np.zeros(n_ev * S, np.uint8), np.zeros(n_ev * S, np.uint8)
+    gp, pg, upd = (np.zeros(n_sub), np.zeros(n_sub), np.zeros(n_ev)) if posterior else (None, None, None)
+    code = engine.lib.phmm_assign_genotypes(
+        engine._h, n_ev, S, P, _p(ao, _lib.u32p), _p(ln, _lib.u32p), _p(kd, _lib.u8p), _p(pl_off, _lib.u64p), _p(pl, _i32p),
+        _p(c_off, _lib.u32p), _p(ca, _lib.u32p), int(method), float(log10_snp_het), float(log10_indel_het), _p(mono, _lib.u8p),
+        _p(s_off, _lib.u64p), _p(sub_pl, _i32p), _p(gt, _i32p), _p(gq, _i32p), _p(log10_gq, _lib.f64p), _p(called, _lib.u8p),
+        _p(sflags, _lib.u8p), _p(gp, _lib.f64p), _p(pg, _lib.f64p), _p(upd, _lib.f64p))
+    if code != _lib.PHMM_OK:
+        raise PhmmError(code, engine.last_error())
+    cut = lambda a: None if a is None else [a[int(s_off[e]):int(s_off[e + 1])].reshape(S, int(Gn[e])) for e in range(n_ev)]  # noqa: E731
+    return AssignResult(call_alleles, cut(sub_pl), gt[:n_ev * S * P].reshape(n_ev, S, P), gq.reshape(n_ev, S), log10_gq.reshape(n_ev, S),
+                        called.reshape(n_ev, S), sflags.reshape(n_ev, S), cut(gp), cut(pg), upd)
+
+
 # ---- the annotation of called events (phmm_annotate_events) ----------------------------------------------------------------
 
 class AlignedReads:
@@ -202,8 +267,10 @@ def annotate_events(engine, batch, likelihoods, keep, read_start, read_end_, rea
     """AD, DP, AF, AC per sample and DP, QD, MQ, BQ per event for a batch of called events (phmm_annotate_events,
     include/phmm.h).  The region / read / event arguments are genotype_likelihoods'; mapq: per read; call_alleles: per event
     the indices of the call's alleles among the event's (reference first; empty: not annotated; call_alleles_of);
-    log10_p_error: per event (NaN: none); aligned: AlignedReads or None (no BQ); sample_called / n_filtered:
-    [n_events, n_samples] or None."""
+    log10_p_error: per event (NaN: none); aligned: AlignedReads or None (no BQ); sample_called: [n_events, n_samples], an
+    AssignResult of assign_genotypes (its sample_called) or None; n_filtered: [n_events, n_samples] or None."""
+    if isinstance(sample_called, AssignResult):
+        sample_called = sample_called.sample_called
     lk = np.ascontiguousarray(likelihoods, np.float64)
     kp = None if keep is None else np.ascontiguousarray(keep, np.uint8)
     rs, re_ = np.ascontiguousarray(read_start, np.int64), np.ascontiguousarray(read_end_, np.int64)

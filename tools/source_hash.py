@@ -14,7 +14,8 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "cigar": ("phmm_cigar_internal.hpp", "phmm_cigar_kernels.hip", "phmm_cigar_device.hpp"),
     "server": ("phmm_server.hpp", "phmm_server_kernels.hip"),
     "genotype": ("phmm_genotype_internal.hpp", "phmm_genotype_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip",
-                 "phmm_annotate_internal.hpp", "phmm_annotate_kernels.hip"),
+                 "phmm_annotate_internal.hpp", "phmm_annotate_kernels.hip", "phmm_assign_internal.hpp",
+                 "phmm_assign_kernels.hip"),
 }
 
 
