@@ -426,7 +426,8 @@ int phmm_realign_to_best(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
  *                      PHMM_PROJECT_UNCHANGED: no best allele or alignment_offset == -1, the read stays as it is (:60-63);
  *                      negative: the reference panics or returns Err for this read (-1 ... -4 CigarBuilder errors in the
  *                      order of cigar_builder.rs, -5 an assert such as "Read goes past end of reference")
- * Returns PHMM_ERR_CIGAR_CAPACITY when an output slot is too small (n_out_cigar holds the sizes).
+ * Returns PHMM_ERR_CIGAR_CAPACITY when an output slot is too small (n_out_cigar holds the sizes).  Of out_cigar only the
+ * elements reported are written: the words of a slot behind them, and the slots of reads that are not realigned, stay.
  */
 #define PHMM_PROJECT_REALIGNED 0
 #define PHMM_PROJECT_UNCHANGED 1

@@ -189,7 +189,12 @@ extern "C" int phmm_project_to_reference(phmm_handle *h, uint32_t n_regions, con
         memcpy(status, W.host + o_st, 4ull * n_reads);
         memcpy(n_out_cigar, W.host + o_no, 4ull * n_reads);
         memcpy(new_pos, W.host + o_np, 8ull * n_reads);
-        if (n_out) memcpy(out_cigar, W.host + o_out, 4ull * n_out);
+        // only what the call reports: a slot's words behind the read's elements, and the slots of reads that are not
+        // realigned, stay as the caller left them (the kernel wrote nothing there: the staging holds older calls' bytes)
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            const uint64_t n = std::min<uint64_t>(n_out_cigar[r], out_cigar_off[r + 1] - out_cigar_off[r]);
+            if (status[r] == CIGAR_OK && n) memcpy(out_cigar + out_cigar_off[r], W.host + o_out + 4ull * out_cigar_off[r], 4ull * n);
+        }
         if (*(const uint32_t *)(W.host + o_fl) & 1u) {
             h->err = "phmm_project_to_reference: a CIGAR needs more elements than its slot holds (n_out_cigar has the sizes)";
             return h->err_code = PHMM_ERR_CIGAR_CAPACITY;
