@@ -8,30 +8,13 @@
 
 #include "phmm_af_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 
 using namespace phmm;
 
+using namespace phmm_host;
+
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 int fail(phmm_handle *h, const std::string &msg) {
     h->err = "phmm_allele_frequency: " + msg;
@@ -53,7 +36,7 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
                           double *log10_p_no_variant, double *log10_p_variant_present, double *log10_p_absent, int64_t *mle_count,
                           uint8_t *allele_flags, double *qual, uint32_t *flags, uint32_t *iterations) {
     if (!h) return PHMM_ERR_INVALID_ARG;
-    try {
+    PHMM_GUARD_BEGIN
         h->err_code = PHMM_OK;
         if (!n_events) return PHMM_OK;
         // ---- arguments: everything is checked before anything is written ----------------------------------------------------
@@ -129,16 +112,13 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
         // ---- the computed events, densely: alleles with their prior pseudo counts, PLs ------------------------------------
         std::vector<uint32_t> c_allele_off(n_c + 1, 0), c_G(n_c);
         std::vector<int32_t> c_span_del(n_c);
-        std::vector<uint64_t> c_pl_off(n_c);
-        uint64_t n_pl = 0;
         for (uint32_t i = 0; i < n_c; ++i) {
             const uint32_t e = computed[i];
             c_allele_off[i + 1] = c_allele_off[i] + (event_allele_off[e + 1] - event_allele_off[e]);
             c_G[i] = G[e];
             c_span_del[i] = span_del[e];
-            c_pl_off[i] = n_pl;
-            n_pl += (uint64_t)n_samples * G[e];
         }
+        const DensePls pls(computed, c_G, n_samples);
         const uint32_t n_al = c_allele_off[n_c];
         std::vector<double> prior(n_al);
         std::vector<uint8_t> kind(n_al, PHMM_AF_KIND_PLAIN);
@@ -173,93 +153,71 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
             }
         }
 
-        DevGuard dg(h->device);
-        auto &W = h->afwork;
+        DeviceGuard dg(h->device);
+        StagingBuffer &W = h->af_staging;
         hipStream_t S = h->streams[0];
         // ---- staging: inputs, then the outputs -----------------------------------------------------------------------------
-        size_t o = 0;
-        auto place = [&](size_t bytes) {
-            const size_t at = o;
-            o += up256(bytes);
-            return at;
-        };
-        const size_t o_wk = place(4ull * work.size()), o_ao = place(4ull * (n_c + 1)), o_gc = place(4ull * n_c),
-                     o_sd = place(4ull * n_c), o_po = place(8ull * n_c), o_pl = place(4ull * n_pl), o_pr = place(8ull * n_al),
-                     o_kd = place(n_al), o_co = place(4ull * (n_gt + 1)), o_c = place(4ull * T.second.size()),
-                     o_lc = place(8ull * n_gt), o_ga = place(8ull * n_gt), o_nl = place(8ull * (AF_MAX_ALLELES + 1)), in_bytes = o;
-        const size_t o_pnv = place(8ull * n_c), o_pvp = place(8ull * n_c), o_q = place(8ull * n_c), o_fl = place(4ull * n_c),
-                     o_it = place(4ull * n_c), o_abs = place(8ull * n_al), o_mle = place(8ull * n_al), o_af = place(n_al), total = o;
-        if (W.cap < total) {
-            (void)hipStreamSynchronize(S);
-            if (W.dev) (void)hipFree(W.dev);
-            if (W.host) (void)hipHostFree(W.host);
-            W.dev = W.host = nullptr;
-            W.cap = 0;
-            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(allele-frequency staging)") ||
-                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(allele-frequency staging)"))
-                return PHMM_ERR_HIP;
-            W.cap = cap;
-        }
-        auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
-        };
-        put(o_wk, work.data(), 4ull * work.size());
-        put(o_ao, c_allele_off.data(), 4ull * (n_c + 1));
-        put(o_gc, c_G.data(), 4ull * n_c);
-        put(o_sd, c_span_del.data(), 4ull * n_c);
-        put(o_po, c_pl_off.data(), 8ull * n_c);
-        for (uint32_t i = 0; i < n_c; ++i) put(o_pl + 4 * c_pl_off[i], pl + pl_off[computed[i]], 4ull * n_samples * c_G[i]);
-        put(o_pr, prior.data(), 8ull * n_al);
-        put(o_kd, kind.data(), n_al);
-        put(o_co, T.first.data(), 4ull * (n_gt + 1));
-        put(o_c, T.second.data(), 4ull * T.second.size());
-        put(o_lc, log10_comb.data(), 8ull * n_gt);
-        put(o_ga, gt_alleles.data(), 8ull * n_gt);
-        put(o_nl, neg_log10_alleles.data(), 8ull * (AF_MAX_ALLELES + 1));
-        h->stat_staged_bytes += in_bytes;
+        StageLayout L;
+        const auto s_wk = L.in(work.data(), work.size()), s_ao = L.in(c_allele_off.data(), n_c + 1), s_gc = L.in(c_G.data(), n_c);
+        const auto s_sd = L.in(c_span_del.data(), n_c);
+        const auto s_po = L.in(pls.off.data(), n_c);
+        const auto s_pl = L.in<int32_t>(pls.n);  // packed below
+        const auto s_pr = L.in(prior.data(), n_al);
+        const auto s_kd = L.in(kind.data(), n_al);
+        const auto s_co = L.in(T.first.data(), T.first.size()), s_c = L.in(T.second.data(), T.second.size());
+        const auto s_lc = L.in(log10_comb.data(), n_gt);
+        const auto s_ga = L.in(gt_alleles.data(), n_gt);
+        const auto s_nl = L.in(neg_log10_alleles.data(), AF_MAX_ALLELES + 1);
+        L.end_inputs();
+        const auto s_pnv = L.out<double>(n_c), s_pvp = L.out<double>(n_c), s_q = L.out<double>(n_c);
+        const auto s_fl = L.out<uint32_t>(n_c), s_it = L.out<uint32_t>(n_c);
+        const auto s_abs = L.out<double>(n_al);
+        const auto s_mle = L.out<int64_t>(n_al);
+        const auto s_af = L.out<uint8_t>(n_al);
+        if (!W.reserve(h, L, "allele-frequency staging")) return PHMM_ERR_HIP;
+        pls.into(W.host_ptr(s_pl), pl_off, pl);
+        h->stat_staged_bytes += L.in_bytes;
 
         AfParams p{};
         p.n_samples = n_samples;
-        p.allele_off = (const uint32_t *)(W.dev + o_ao);
-        p.genotype_count = (const uint32_t *)(W.dev + o_gc);
-        p.span_del = (const int32_t *)(W.dev + o_sd);
-        p.pl_off = (const uint64_t *)(W.dev + o_po);
-        p.pl = (const int32_t *)(W.dev + o_pl);
-        p.prior = (const double *)(W.dev + o_pr);
-        p.kind = (const uint8_t *)(W.dev + o_kd);
-        p.gt_comp_off = (const uint32_t *)(W.dev + o_co);
-        p.gt_comp = (const uint32_t *)(W.dev + o_c);
-        p.gt_log10_comb = (const double *)(W.dev + o_lc);
-        p.gt_alleles = (const uint64_t *)(W.dev + o_ga);
-        p.neg_log10_alleles = (const double *)(W.dev + o_nl);
+        p.allele_off = W.dev_ptr(s_ao);
+        p.genotype_count = W.dev_ptr(s_gc);
+        p.span_del = W.dev_ptr(s_sd);
+        p.pl_off = W.dev_ptr(s_po);
+        p.pl = W.dev_ptr(s_pl);
+        p.prior = W.dev_ptr(s_pr);
+        p.kind = W.dev_ptr(s_kd);
+        p.gt_comp_off = W.dev_ptr(s_co);
+        p.gt_comp = W.dev_ptr(s_c);
+        p.gt_log10_comb = W.dev_ptr(s_lc);
+        p.gt_alleles = W.dev_ptr(s_ga);
+        p.neg_log10_alleles = W.dev_ptr(s_nl);
         p.stand_min_conf = stand_min_conf;
         p.log_10 = std::log(10.0);
         p.inv_log_10 = 1.0 / p.log_10;
         p.log1mexp_threshold = std::log(0.5);
-        p.log10_p_no_variant = (double *)(W.dev + o_pnv);
-        p.log10_p_variant_present = (double *)(W.dev + o_pvp);
-        p.qual = (double *)(W.dev + o_q);
-        p.flags = (uint32_t *)(W.dev + o_fl);
-        p.iterations = (uint32_t *)(W.dev + o_it);
-        p.log10_p_absent = (double *)(W.dev + o_abs);
-        p.mle_count = (int64_t *)(W.dev + o_mle);
-        p.allele_flags = (uint8_t *)(W.dev + o_af);
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes, hipMemcpyHostToDevice, S), "H2D allele frequency")) return PHMM_ERR_HIP;
+        p.log10_p_no_variant = W.dev_ptr(s_pnv);
+        p.log10_p_variant_present = W.dev_ptr(s_pvp);
+        p.qual = W.dev_ptr(s_q);
+        p.flags = W.dev_ptr(s_fl);
+        p.iterations = W.dev_ptr(s_it);
+        p.log10_p_absent = W.dev_ptr(s_abs);
+        p.mle_count = W.dev_ptr(s_mle);
+        p.allele_flags = W.dev_ptr(s_af);
+        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D allele frequency")) return PHMM_ERR_HIP;
         for (int c = 0; c < 4; ++c) {
-            p.work = (const uint32_t *)(W.dev + o_wk) + cls_off[c][0];
+            p.work = W.dev_ptr(s_wk) + cls_off[c][0];
             p.n_wave_events = cls_off[c][1];
             p.n_block_events = cls_off[c][2];
-            if (!ok(h, launch_af(p, classes[c], S), "phmm_af_kernel")) return PHMM_ERR_HIP;
+            if (!hip_ok(h, launch_af(p, classes[c], S), "phmm_af_kernel")) return PHMM_ERR_HIP;
         }
-        if (!ok(h, hipMemcpyAsync(W.host + o_pnv, W.dev + o_pnv, total - o_pnv, hipMemcpyDeviceToHost, S), "D2H allele frequency") ||
-            !ok(h, hipStreamSynchronize(S), "sync(allele frequency)"))
+        if (!hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H allele frequency") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(allele frequency)"))
             return PHMM_ERR_HIP;
-        const double *r_pnv = (const double *)(W.host + o_pnv), *r_pvp = (const double *)(W.host + o_pvp),
-                     *r_q = (const double *)(W.host + o_q), *r_abs = (const double *)(W.host + o_abs);
-        const uint32_t *r_fl = (const uint32_t *)(W.host + o_fl), *r_it = (const uint32_t *)(W.host + o_it);
-        const int64_t *r_mle = (const int64_t *)(W.host + o_mle);
-        const uint8_t *r_af = (const uint8_t *)(W.host + o_af);
+        const double *r_pnv = W.host_ptr(s_pnv), *r_pvp = W.host_ptr(s_pvp), *r_q = W.host_ptr(s_q), *r_abs = W.host_ptr(s_abs);
+        const uint32_t *r_fl = W.host_ptr(s_fl), *r_it = W.host_ptr(s_it);
+        const int64_t *r_mle = W.host_ptr(s_mle);
+        const uint8_t *r_af = W.host_ptr(s_af);
         for (uint32_t i = 0; i < n_c; ++i) {
             const uint32_t e = computed[i], a0 = event_allele_off[e], c0 = c_allele_off[i], A = c_allele_off[i + 1] - c0;
             log10_p_no_variant[e] = r_pnv[i];
@@ -272,13 +230,7 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
             if (allele_flags) memcpy(allele_flags + a0, r_af + c0, A);
         }
         return PHMM_OK;
-    } catch (const std::bad_alloc &) {
-        h->err = "phmm_allele_frequency: out of host memory";
-        return h->err_code = PHMM_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        h->err = std::string("phmm_allele_frequency: ") + e.what();
-        return h->err_code = PHMM_ERR_INTERNAL;
-    }
+    PHMM_GUARD_END(h, "phmm_allele_frequency", PHMM_FAIL_CODE)
 }
 
 }  // extern "C"

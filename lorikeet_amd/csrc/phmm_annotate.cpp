@@ -8,30 +8,13 @@
 
 #include "phmm_annotate_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 
 using namespace phmm;
 
+using namespace phmm_host;
+
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 int fail(phmm_handle *h, const std::string &msg) {
     h->err = "phmm_annotate_events: " + msg;
@@ -54,7 +37,7 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
                          int32_t *dp, double *af, uint32_t *ac, uint8_t *mq, uint8_t *bq, int32_t *info_dp, int32_t *qd_depth,
                          double *qd, uint32_t *flags) {
     if (!h) return PHMM_ERR_INVALID_ARG;
-    try {
+    PHMM_GUARD_BEGIN
         h->err_code = PHMM_OK;
         if (!n_events) return PHMM_OK;
         // ---- arguments: everything is checked before anything is written ----------------------------------------------------
@@ -123,13 +106,7 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
             max_call = std::max(max_call, C);
         }
         const size_t n_call = call_off[n_events];
-        std::vector<uint64_t> lk_off(n_regions, 0);
-        uint64_t n_lk = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            if (!region_used[g]) continue;
-            lk_off[g] = n_lk;
-            n_lk += (uint64_t)(region_read_off[g + 1] - region_read_off[g]) * (region_hap_off[g + 1] - region_hap_off[g]);
-        }
+        const LikelihoodGather lks(n_regions, region_read_off, region_hap_off, region_used);
         // the subset map of the call (haplotype_caller_genotyping_engine.rs:376-384) composed with the event's: haplotype -> index in
         // the call, -1 for a haplotype on no allele or on one the call leaves out
         std::vector<int32_t> hap_call(n_map), inverse(ANN_MAX_ALLELES);
@@ -144,147 +121,111 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
             }
         }
 
-        DevGuard dg(h->device);
-        phmm_handle::AnnWork &W = h->annwork;
+        DeviceGuard dg(h->device);
+        StagingBuffer &W = h->annotate_staging;
         hipStream_t S = h->streams[0];
         // ---- staging: inputs, then the results ------------------------------------------------------------------------------------
-        size_t o = 0;
-        auto place = [&](size_t bytes) {
-            const size_t at = o;
-            o += up256(bytes);
-            return at;
-        };
         const size_t n_es = (size_t)n_events * n_samples, n_bases = with_bq ? read_off[n_reads] : 0;
-        const size_t o_rro = place(4ull * (n_regions + 1)), o_rho = place(4ull * (n_regions + 1)), o_lko = place(8ull * n_regions),
-                     o_lk = place(8ull * n_lk), o_kp = place(n_reads), o_rs = place(4ull * n_reads), o_st = place(8ull * n_reads),
-                     o_en = place(8ull * n_reads), o_mapq = place(n_reads), o_er = place(4ull * n_events), o_emo = place(4ull * n_events),
-                     o_map = place(4ull * n_map), o_co = place(4ull * (n_events + 1)), o_es = place(8ull * n_events),
-                     o_ee = place(8ull * n_events), o_err = place(8ull * n_events), o_sc = place(sample_called ? n_es : 0),
-                     o_nf = place(n_filtered ? 4ull * n_es : 0), o_ro = place(with_bq ? 4ull * (n_reads + 1) : 0), o_bq = place(n_bases),
-                     o_cgo = place(with_bq ? 4ull * (n_reads + 1) : 0), o_cg = place(4ull * n_cigar),
-                     o_ss = place(with_bq ? 8ull * n_reads : 0), o_ep = place(with_bq ? 8ull * n_events : 0), in_bytes = o;
-        const size_t o_af = place(8ull * n_call * n_samples), o_qd = place(8ull * n_events), o_ad = place(4ull * n_call * n_samples),
-                     o_dp = place(4ull * n_es), o_ac = place(4ull * n_es), o_idp = place(4ull * n_events), o_qdd = place(4ull * n_events),
-                     o_fl = place(4ull * n_events), o_mq = place(n_call), o_obq = place(with_bq ? n_call : 0), total = o;
-        if (W.cap < total) {
-            (void)hipStreamSynchronize(S);
-            if (W.dev) (void)hipFree(W.dev);
-            if (W.host) (void)hipHostFree(W.host);
-            W.dev = W.host = nullptr;
-            W.cap = 0;
-            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(annotate staging)") ||
-                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(annotate staging)"))
-                return PHMM_ERR_HIP;
-            W.cap = cap;
-        }
-        auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
-        };
-        put(o_rro, region_read_off, 4ull * (n_regions + 1));
-        put(o_rho, region_hap_off, 4ull * (n_regions + 1));
-        put(o_lko, lk_off.data(), 8ull * n_regions);
-        for (uint32_t g = 0; g < n_regions; ++g)
-            if (region_used[g])
-                put(o_lk + 8 * lk_off[g], likelihoods + out_off[g],
-                    8ull * (region_read_off[g + 1] - region_read_off[g]) * (region_hap_off[g + 1] - region_hap_off[g]));
-        if (keep) put(o_kp, keep, n_reads);
-        else if (n_reads) memset(W.host + o_kp, 1, n_reads);
-        put(o_rs, read_sample, 4ull * n_reads);
-        put(o_st, read_start, 8ull * n_reads);
-        put(o_en, read_end, 8ull * n_reads);
-        put(o_mapq, mapq, n_reads);
-        put(o_er, event_region, 4ull * n_events);
-        put(o_emo, map_off.data(), 4ull * n_events);
-        put(o_map, hap_call.data(), 4ull * n_map);
-        put(o_co, call_off.data(), 4ull * (n_events + 1));
-        put(o_es, event_start, 8ull * n_events);
-        put(o_ee, event_end, 8ull * n_events);
-        put(o_err, log10_p_error, 8ull * n_events);
-        if (sample_called) put(o_sc, sample_called, n_es);
-        if (n_filtered) put(o_nf, n_filtered, 4ull * n_es);
+        StageLayout L;
+        const auto s_rro = L.in(region_read_off, n_regions + 1), s_rho = L.in(region_hap_off, n_regions + 1);
+        const auto s_lko = L.in(lks.off.data(), n_regions);
+        const auto s_lk = L.in<double>(lks.n);
+        const auto s_kp = L.in<uint8_t>(n_reads);
+        const auto s_rs = L.in(read_sample, n_reads);
+        const auto s_st = L.in(read_start, n_reads), s_en = L.in(read_end, n_reads);
+        const auto s_mapq = L.in(mapq, n_reads);
+        const auto s_er = L.in(event_region, n_events), s_emo = L.in(map_off.data(), n_events);
+        const auto s_map = L.in(hap_call.data(), n_map);
+        const auto s_co = L.in(call_off.data(), n_events + 1);
+        const auto s_es = L.in(event_start, n_events), s_ee = L.in(event_end, n_events);
+        const auto s_err = L.in(log10_p_error, n_events);
+        const auto s_sc = L.in(sample_called, sample_called ? n_es : 0);
+        const auto s_nf = L.in(n_filtered, n_filtered ? n_es : 0);
+        const auto s_ro = L.in(read_off, with_bq ? n_reads + 1 : 0);
+        const auto s_bq = L.in(base_q, n_bases);
+        const auto s_cgo = L.in<uint32_t>(with_bq ? n_reads + 1 : 0), s_cg = L.in<uint32_t>(n_cigar);  // the CIGARs, repacked densely below
+        const auto s_ss = L.in(read_soft_start, with_bq ? n_reads : 0), s_ep = L.in(event_pos, with_bq ? n_events : 0);
+        L.end_inputs();
+        const auto s_af = L.out<double>(n_call * n_samples), s_qd = L.out<double>(n_events);
+        const auto s_ad = L.out<int32_t>(n_call * n_samples), s_dp = L.out<int32_t>(n_es);
+        const auto s_ac = L.out<uint32_t>(n_es);
+        const auto s_idp = L.out<int32_t>(n_events), s_qdd = L.out<int32_t>(n_events);
+        const auto s_fl = L.out<uint32_t>(n_events);
+        const auto s_mq = L.out<uint8_t>(n_call), s_obq = L.out<uint8_t>(with_bq ? n_call : 0);
+        if (!W.reserve(h, L, "annotate staging")) return PHMM_ERR_HIP;
+        lks.into(W.host_ptr(s_lk), W.host_ptr(s_kp), out_off, likelihoods, keep);
         if (with_bq) {
-            put(o_ro, read_off, 4ull * (n_reads + 1));
-            put(o_bq, base_q, n_bases);
-            uint32_t *cgo = (uint32_t *)(W.host + o_cgo), at = 0;
+            uint32_t *cgo = W.host_ptr(s_cgo), *cg = W.host_ptr(s_cg), at = 0;
             for (uint32_t r = 0; r < n_reads; ++r) {
                 cgo[r] = at;
-                put(o_cg + 4ull * at, out_cigar + out_cigar_off[r], 4ull * n_out_cigar[r]);
+                if (n_out_cigar[r]) memcpy(cg + at, out_cigar + out_cigar_off[r], 4ull * n_out_cigar[r]);
                 at += n_out_cigar[r];
             }
             cgo[n_reads] = at;
-            put(o_ss, read_soft_start, 8ull * n_reads);
-            put(o_ep, event_pos, 8ull * n_events);
         }
-        h->stat_staged_bytes += in_bytes;
+        h->stat_staged_bytes += L.in_bytes;
 
         AnnotateParams p{};
         p.n_events = n_events;
         p.n_samples = n_samples;
-        p.region_read_off = (const uint32_t *)(W.dev + o_rro);
-        p.region_hap_off = (const uint32_t *)(W.dev + o_rho);
-        p.region_lk_off = (const uint64_t *)(W.dev + o_lko);
-        p.likelihoods = (const double *)(W.dev + o_lk);
-        p.keep = (const uint8_t *)(W.dev + o_kp);
-        p.read_sample = (const uint32_t *)(W.dev + o_rs);
-        p.read_start = (const int64_t *)(W.dev + o_st);
-        p.read_end = (const int64_t *)(W.dev + o_en);
-        p.mapq = (const uint8_t *)(W.dev + o_mapq);
-        p.event_region = (const uint32_t *)(W.dev + o_er);
-        p.event_map_off = (const uint32_t *)(W.dev + o_emo);
-        p.event_hap_call = (const int32_t *)(W.dev + o_map);
-        p.call_off = (const uint32_t *)(W.dev + o_co);
-        p.event_start = (const int64_t *)(W.dev + o_es);
-        p.event_end = (const int64_t *)(W.dev + o_ee);
-        p.log10_p_error = (const double *)(W.dev + o_err);
-        p.sample_called = sample_called ? (const uint8_t *)(W.dev + o_sc) : nullptr;
-        p.n_filtered = n_filtered ? (const uint32_t *)(W.dev + o_nf) : nullptr;
+        p.region_read_off = W.dev_ptr(s_rro);
+        p.region_hap_off = W.dev_ptr(s_rho);
+        p.region_lk_off = W.dev_ptr(s_lko);
+        p.likelihoods = W.dev_ptr(s_lk);
+        p.keep = W.dev_ptr(s_kp);
+        p.read_sample = W.dev_ptr(s_rs);
+        p.read_start = W.dev_ptr(s_st);
+        p.read_end = W.dev_ptr(s_en);
+        p.mapq = W.dev_ptr(s_mapq);
+        p.event_region = W.dev_ptr(s_er);
+        p.event_map_off = W.dev_ptr(s_emo);
+        p.event_hap_call = W.dev_ptr(s_map);
+        p.call_off = W.dev_ptr(s_co);
+        p.event_start = W.dev_ptr(s_es);
+        p.event_end = W.dev_ptr(s_ee);
+        p.log10_p_error = W.dev_ptr(s_err);
+        p.sample_called = sample_called ? W.dev_ptr(s_sc) : nullptr;
+        p.n_filtered = n_filtered ? W.dev_ptr(s_nf) : nullptr;
         if (with_bq) {
-            p.read_off = (const uint32_t *)(W.dev + o_ro);
-            p.base_q = (const uint8_t *)(W.dev + o_bq);
-            p.cigar_off = (const uint32_t *)(W.dev + o_cgo);
-            p.cigar = (const uint32_t *)(W.dev + o_cg);
-            p.read_soft_start = (const int64_t *)(W.dev + o_ss);
-            p.event_pos = (const int64_t *)(W.dev + o_ep);
-            p.bq = (uint8_t *)(W.dev + o_obq);
+            p.read_off = W.dev_ptr(s_ro);
+            p.base_q = W.dev_ptr(s_bq);
+            p.cigar_off = W.dev_ptr(s_cgo);
+            p.cigar = W.dev_ptr(s_cg);
+            p.read_soft_start = W.dev_ptr(s_ss);
+            p.event_pos = W.dev_ptr(s_ep);
+            p.bq = W.dev_ptr(s_obq);
         }
-        p.af = (double *)(W.dev + o_af);
-        p.qd = (double *)(W.dev + o_qd);
-        p.ad = (int32_t *)(W.dev + o_ad);
-        p.dp = (int32_t *)(W.dev + o_dp);
-        p.ac = (uint32_t *)(W.dev + o_ac);
-        p.info_dp = (int32_t *)(W.dev + o_idp);
-        p.qd_depth = (int32_t *)(W.dev + o_qdd);
-        p.flags = (uint32_t *)(W.dev + o_fl);
-        p.mq = (uint8_t *)(W.dev + o_mq);
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes, hipMemcpyHostToDevice, S), "H2D annotate") ||
-            !ok(h, launch_annotate(p, max_call, S), "phmm_annotate_kernel") ||
-            !ok(h, hipMemcpyAsync(W.host + o_af, W.dev + o_af, total - o_af, hipMemcpyDeviceToHost, S), "D2H annotate") ||
-            !ok(h, hipStreamSynchronize(S), "sync(annotate)"))
+        p.af = W.dev_ptr(s_af);
+        p.qd = W.dev_ptr(s_qd);
+        p.ad = W.dev_ptr(s_ad);
+        p.dp = W.dev_ptr(s_dp);
+        p.ac = W.dev_ptr(s_ac);
+        p.info_dp = W.dev_ptr(s_idp);
+        p.qd_depth = W.dev_ptr(s_qdd);
+        p.flags = W.dev_ptr(s_fl);
+        p.mq = W.dev_ptr(s_mq);
+        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D annotate") ||
+            !hip_ok(h, launch_annotate(p, max_call, S), "phmm_annotate_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H annotate") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(annotate)"))
             return PHMM_ERR_HIP;
         // per allele and per (sample, allele) results go to the caller's call_allele_off offsets, the rest is dense
         for (uint32_t e = 0; e < n_events; ++e) {
             const size_t C = call_off[e + 1] - call_off[e], at = call_allele_off[e], from = call_off[e];
             if (!C) continue;
-            memcpy(ad + at * n_samples, W.host + o_ad + 4 * from * n_samples, 4 * C * n_samples);
-            memcpy(af + at * n_samples, W.host + o_af + 8 * from * n_samples, 8 * C * n_samples);
-            memcpy(mq + at, W.host + o_mq + from, C);
-            if (with_bq) memcpy(bq + at, W.host + o_obq + from, C);
+            memcpy(ad + at * n_samples, W.host_ptr(s_ad) + from * n_samples, 4 * C * n_samples);
+            memcpy(af + at * n_samples, W.host_ptr(s_af) + from * n_samples, 8 * C * n_samples);
+            memcpy(mq + at, W.host_ptr(s_mq) + from, C);
+            if (with_bq) memcpy(bq + at, W.host_ptr(s_obq) + from, C);
         }
-        memcpy(dp, W.host + o_dp, 4 * n_es);
-        memcpy(ac, W.host + o_ac, 4 * n_es);
-        memcpy(info_dp, W.host + o_idp, 4ull * n_events);
-        memcpy(qd_depth, W.host + o_qdd, 4ull * n_events);
-        memcpy(qd, W.host + o_qd, 8ull * n_events);
-        memcpy(flags, W.host + o_fl, 4ull * n_events);
+        memcpy(dp, W.host_ptr(s_dp), 4 * n_es);
+        memcpy(ac, W.host_ptr(s_ac), 4 * n_es);
+        memcpy(info_dp, W.host_ptr(s_idp), 4ull * n_events);
+        memcpy(qd_depth, W.host_ptr(s_qdd), 4ull * n_events);
+        memcpy(qd, W.host_ptr(s_qd), 8ull * n_events);
+        memcpy(flags, W.host_ptr(s_fl), 4ull * n_events);
         return PHMM_OK;
-    } catch (const std::bad_alloc &) {
-        h->err = "phmm_annotate_events: out of host memory";
-        return h->err_code = PHMM_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        h->err = std::string("phmm_annotate_events: ") + e.what();
-        return h->err_code = PHMM_ERR_INTERNAL;
-    }
+    PHMM_GUARD_END(h, "phmm_annotate_events", PHMM_FAIL_CODE)
 }
 
 }  // extern "C"

@@ -31,11 +31,13 @@
 
 #include "phmm_cigar_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 #include <sched.h>
 #include "phmm_internal.hpp"
 #include "phmm_tables.hpp"
 
 using namespace phmm;
+using namespace phmm_host;
 
 namespace {
 
@@ -76,19 +78,6 @@ static const int kForcedEagerD2H = getenv("PHMM_EAGER_D2H") ? atoi(getenv("PHMM_
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Entry points leave the calling thread's current HIP device as they found it.
-struct DeviceGuard {
-    int prev = -1, dev;
-    bool ok = true;
-    explicit DeviceGuard(int device) : dev(device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
 struct ShapeClass {
     int L = 0, K = 0;  // L == 0 -> generic kernel
     std::vector<uint32_t> reads;  // global read indices (host copy; uploaded unless identity)
@@ -119,6 +108,11 @@ struct ShapeClass {
 };
 
 }  // namespace
+
+void phmm_host::set_create_error(const std::string &msg) {
+    std::lock_guard<std::mutex> g(g_err_mu);
+    g_create_err = msg;
+}
 
 struct phmm_batch {
     phmm_handle *h = nullptr;
@@ -164,54 +158,10 @@ struct phmm_batch {
 
 namespace {
 
-bool hip_ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    if (h) {
-        h->err = buf;
-        h->err_code = PHMM_ERR_HIP;
-    }
-    else {
-        std::lock_guard<std::mutex> g(g_err_mu);
-        g_create_err = buf;
-    }
-    return false;
-}
 #define HIP_TRY(h, call, ret)                  \
     do {                                       \
         if (!hip_ok((h), (call), #call)) return ret; \
     } while (0)
-
-// No C++ exception crosses the C ABI: every extern "C" body that can allocate runs inside PHMM_GUARD.
-int on_exception(phmm_handle *h, const char *where, const char *what, int code) {
-    std::string msg = std::string(where) + ": " + what;
-    if (h) {
-        h->err = msg;
-        h->err_code = code;
-    } else {
-        std::lock_guard<std::mutex> g(g_err_mu);
-        g_create_err = msg;
-    }
-    return code;
-}
-#define PHMM_GUARD_BEGIN try {
-#define PHMM_GUARD_END(h, where, fail)                                                                    \
-    }                                                                                                     \
-    catch (const std::bad_alloc &) {                                                                      \
-        (void)on_exception((h), (where), "out of host memory", PHMM_ERR_NO_MEMORY);                       \
-        return fail(PHMM_ERR_NO_MEMORY);                                                                  \
-    }                                                                                                     \
-    catch (const std::exception &e) {                                                                     \
-        (void)on_exception((h), (where), e.what(), PHMM_ERR_INTERNAL);                                    \
-        return fail(PHMM_ERR_INTERNAL);                                                                   \
-    }                                                                                                     \
-    catch (...) {                                                                                         \
-        (void)on_exception((h), (where), "unknown exception", PHMM_ERR_INTERNAL);                         \
-        return fail(PHMM_ERR_INTERNAL);                                                                   \
-    }
-#define PHMM_FAIL_CODE(c) (c)
-#define PHMM_FAIL_NULL(c) nullptr
 
 int round_up_k(int k) {
     for (int i = 0; i < kNumInstantiatedK; ++i)
@@ -308,8 +258,7 @@ const char *phmm_last_error(phmm_handle *h) {
 phmm_handle *phmm_create(int device_id, unsigned flags) {
     int n = phmm_device_count();
     if (device_id < 0 || device_id >= n || device_id >= kMaxDevices) {
-        std::lock_guard<std::mutex> g(g_err_mu);
-        g_create_err = "phmm_create: no HIP device with that id (this engine has no CPU fallback)";
+        set_create_error("phmm_create: no HIP device with that id (this engine has no CPU fallback)");
         return nullptr;
     }
     DeviceGuard dg(device_id);
@@ -390,20 +339,11 @@ void phmm_destroy(phmm_handle *h) {
         if (h->arenas[i].host) (void)hipHostFree(h->arenas[i].host);
         if (h->arenas[i].rescue) (void)hipFree(h->arenas[i].rescue);
     }
-    if (h->swork.dev) (void)hipFree(h->swork.dev);
-    if (h->swork.host) (void)hipHostFree(h->swork.host);
+    for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging}) b->release();
     if (h->swork.slab) (void)hipFree(h->swork.slab);
     if (h->swork.ws) (void)hipFree(h->swork.ws);
     if (h->swork.ext) (void)hipFree(h->swork.ext);
-    if (h->gwork.dev) (void)hipFree(h->gwork.dev);
-    if (h->gwork.host) (void)hipHostFree(h->gwork.host);
     if (h->gwork.d_jacobian) (void)hipFree(h->gwork.d_jacobian);
-    if (h->afwork.dev) (void)hipFree(h->afwork.dev);
-    if (h->afwork.host) (void)hipHostFree(h->afwork.host);
-    if (h->annwork.dev) (void)hipFree(h->annwork.dev);
-    if (h->annwork.host) (void)hipHostFree(h->annwork.host);
-    if (h->aswork.dev) (void)hipFree(h->aswork.dev);
-    if (h->aswork.host) (void)hipHostFree(h->aswork.host);
     for (int c = 0; c < phmm_handle::SwWork::kMaxChunks; ++c)
         for (hipEvent_t e : {h->swork.ev_in[c], h->swork.ev_out[c], h->swork.ev_k0[c], h->swork.ev_k1[c]})
             if (e) (void)hipEventDestroy(e);
@@ -565,7 +505,6 @@ const char *validate_offsets(uint32_t n_regions, const uint32_t *region_read_off
 }
 
 }  // namespace phmm_host
-using namespace phmm_host;
 
 // (`dry`: plan only -- no device is touched, every "device" pointer of the batch stays null: phmm_plan_describe)
 static phmm_batch *batch_create_impl(phmm_handle *h, uint32_t n_regions, const uint32_t *region_read_off,

@@ -10,30 +10,13 @@
 
 #include "phmm_assign_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 
 using namespace phmm;
 
+using namespace phmm_host;
+
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 int fail(phmm_handle *h, const std::string &msg) {
     h->err = "phmm_assign_genotypes: " + msg;
@@ -51,7 +34,7 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
                           int32_t *gt, int32_t *gq, double *log10_gq, uint8_t *sample_called, uint8_t *sample_flags, double *gp,
                           double *pg, double *log10_p_error_posterior) {
     if (!h) return PHMM_ERR_INVALID_ARG;
-    try {
+    PHMM_GUARD_BEGIN
         h->err_code = PHMM_OK;
         if (!n_events) return PHMM_OK;
         // ---- arguments: everything is checked before anything is written ----------------------------------------------------
@@ -133,20 +116,19 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
 
         // ---- the computed events, densely ------------------------------------------------------------------------------------
         std::vector<uint32_t> c_call_off(n_c + 1, 0), c_G(n_c), c_Gn(n_c);
-        std::vector<uint64_t> c_pl_off(n_c), c_out_off(n_c);
+        std::vector<uint64_t> c_out_off(n_c);
         std::vector<uint8_t> c_mono(n_c, 0);
-        uint64_t n_pl = 0, n_out = 0;
+        uint64_t n_out = 0;
         for (uint32_t i = 0; i < n_c; ++i) {
             const uint32_t e = computed[i];
             c_call_off[i + 1] = c_call_off[i] + (call_allele_off[e + 1] - call_allele_off[e]);
             c_G[i] = G[e];
             c_Gn[i] = Gn[e];
-            c_pl_off[i] = n_pl;
             c_out_off[i] = n_out;
-            n_pl += (uint64_t)n_samples * G[e];
             n_out += (uint64_t)n_samples * Gn[e];
             if (site_monomorphic) c_mono[i] = site_monomorphic[e] != 0;
         }
+        const DensePls pls(computed, c_G, n_samples);
         const uint32_t n_call = c_call_off[n_c];
         std::vector<uint32_t> c_call(n_call);
         std::vector<uint8_t> c_kind(n_call, PHMM_AF_KIND_PLAIN), c_type(n_call, 0);
@@ -161,71 +143,44 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
             }
         }
 
-        DevGuard dg(h->device);
-        auto &W = h->aswork;
+        DeviceGuard dg(h->device);
+        StagingBuffer &W = h->assign_staging;
         hipStream_t S = h->streams[0];
         // ---- staging: inputs, then the outputs -----------------------------------------------------------------------------
-        size_t o = 0;
-        auto place = [&](size_t bytes) {
-            const size_t at = o;
-            o += up256(bytes);
-            return at;
-        };
         const size_t n_es = (size_t)n_c * n_samples;
-        const size_t o_gc = place(4ull * n_c), o_sc = place(4ull * n_c), o_co = place(4ull * (n_c + 1)), o_ca = place(4ull * n_call),
-                     o_kd = place(n_call), o_ty = place(n_call), o_po = place(8ull * n_c), o_pl = place(4ull * n_pl), o_mo = place(n_c),
-                     o_to = place(4ull * T.first.size()), o_tc = place(4ull * T.second.size()), o_rk = place(4ull * rank.size()),
-                     o_oo = place(8ull * n_c), in_bytes = o;
-        const size_t o_pna = place(8ull * n_es);  // device scratch, not copied back
-        const size_t o_gp = place(posteriors ? 8ull * n_out : 0), o_pg = place(posteriors ? 8ull * n_out : 0), o_lq = place(8ull * n_es),
-                     o_qu = place(8ull * n_c), o_sp = place(4ull * n_out), o_gt = place(4ull * n_es * ploidy), o_gq = place(4ull * n_es),
-                     o_cl = place(n_es), o_fl = place(n_es), total = o;
-        if (W.cap < total) {
-            (void)hipStreamSynchronize(S);
-            if (W.dev) (void)hipFree(W.dev);
-            if (W.host) (void)hipHostFree(W.host);
-            W.dev = W.host = nullptr;
-            W.cap = 0;
-            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(genotype assignment staging)") ||
-                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(genotype assignment staging)"))
-                return PHMM_ERR_HIP;
-            W.cap = cap;
-        }
-        auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
-        };
-        put(o_gc, c_G.data(), 4ull * n_c);
-        put(o_sc, c_Gn.data(), 4ull * n_c);
-        put(o_co, c_call_off.data(), 4ull * (n_c + 1));
-        put(o_ca, c_call.data(), 4ull * n_call);
-        put(o_kd, c_kind.data(), n_call);
-        put(o_ty, c_type.data(), n_call);
-        put(o_po, c_pl_off.data(), 8ull * n_c);
-        for (uint32_t i = 0; i < n_c; ++i) put(o_pl + 4 * c_pl_off[i], pl + pl_off[computed[i]], 4ull * n_samples * c_G[i]);
-        put(o_mo, c_mono.data(), n_c);
-        put(o_to, T.first.data(), 4ull * T.first.size());
-        put(o_tc, T.second.data(), 4ull * T.second.size());
-        put(o_rk, rank.data(), 4ull * rank.size());
-        put(o_oo, c_out_off.data(), 8ull * n_c);
-        h->stat_staged_bytes += in_bytes;
+        StageLayout L;
+        const auto s_gc = L.in(c_G.data(), n_c), s_sc = L.in(c_Gn.data(), n_c), s_co = L.in(c_call_off.data(), n_c + 1), s_ca = L.in(c_call.data(), n_call);
+        const auto s_kd = L.in(c_kind.data(), n_call), s_ty = L.in(c_type.data(), n_call);
+        const auto s_po = L.in(pls.off.data(), n_c);
+        const auto s_pl = L.in<int32_t>(pls.n);  // packed below
+        const auto s_mo = L.in(c_mono.data(), n_c);
+        const auto s_to = L.in(T.first.data(), T.first.size()), s_tc = L.in(T.second.data(), T.second.size()), s_rk = L.in(rank.data(), rank.size());
+        const auto s_oo = L.in(c_out_off.data(), n_c);
+        L.end_inputs();
+        const auto s_pna = L.scratch<double>(n_es);
+        const auto s_gp = L.out<double>(posteriors ? n_out : 0), s_pg = L.out<double>(posteriors ? n_out : 0), s_lq = L.out<double>(n_es), s_qu = L.out<double>(n_c);
+        const auto s_sp = L.out<int32_t>(n_out), s_gt = L.out<int32_t>(n_es * ploidy), s_gq = L.out<int32_t>(n_es);
+        const auto s_cl = L.out<uint8_t>(n_es), s_fl = L.out<uint8_t>(n_es);
+        if (!W.reserve(h, L, "genotype assignment staging")) return PHMM_ERR_HIP;
+        pls.into(W.host_ptr(s_pl), pl_off, pl);
+        h->stat_staged_bytes += L.in_bytes;
 
         AssignParams p{};
         p.n_samples = n_samples;
         p.ploidy = ploidy;
         p.method = posteriors ? AS_USE_POSTERIORS : AS_USE_PLS;
-        p.genotype_count = (const uint32_t *)(W.dev + o_gc);
-        p.sub_count = (const uint32_t *)(W.dev + o_sc);
-        p.call_off = (const uint32_t *)(W.dev + o_co);
-        p.call_allele = (const uint32_t *)(W.dev + o_ca);
-        p.call_kind = (const uint8_t *)(W.dev + o_kd);
-        p.call_type = (const uint8_t *)(W.dev + o_ty);
-        p.pl_off = (const uint64_t *)(W.dev + o_po);
-        p.pl = (const int32_t *)(W.dev + o_pl);
-        p.monomorphic = (const uint8_t *)(W.dev + o_mo);
-        p.gt_comp_off = (const uint32_t *)(W.dev + o_to);
-        p.gt_comp = (const uint32_t *)(W.dev + o_tc);
-        p.rank_off = (const uint32_t *)(W.dev + o_rk);
+        p.genotype_count = W.dev_ptr(s_gc);
+        p.sub_count = W.dev_ptr(s_sc);
+        p.call_off = W.dev_ptr(s_co);
+        p.call_allele = W.dev_ptr(s_ca);
+        p.call_kind = W.dev_ptr(s_kd);
+        p.call_type = W.dev_ptr(s_ty);
+        p.pl_off = W.dev_ptr(s_po);
+        p.pl = W.dev_ptr(s_pl);
+        p.monomorphic = W.dev_ptr(s_mo);
+        p.gt_comp_off = W.dev_ptr(s_to);
+        p.gt_comp = W.dev_ptr(s_tc);
+        p.rank_off = W.dev_ptr(s_rk);
         p.rank_stride = stride;
         if (posteriors) {
             // GenotypePriorCalculator::assuming_hw with other_het = None (genotype_prior_calculator.rs:46-80, :116-139), by
@@ -242,45 +197,39 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
         p.log_10 = std::log(10.0);
         p.inv_log_10 = 1.0 / p.log_10;
         p.log1mexp_threshold = std::log(0.5);
-        p.out_off = (const uint64_t *)(W.dev + o_oo);
-        p.sub_pl = (int32_t *)(W.dev + o_sp);
-        p.gp = (double *)(W.dev + o_gp);
-        p.pg = (double *)(W.dev + o_pg);
-        p.gt = (int32_t *)(W.dev + o_gt);
-        p.gq = (int32_t *)(W.dev + o_gq);
-        p.log10_gq = (double *)(W.dev + o_lq);
-        p.called = (uint8_t *)(W.dev + o_cl);
-        p.flags = (uint8_t *)(W.dev + o_fl);
-        p.p_no_alt = (double *)(W.dev + o_pna);
-        p.qual_update = (double *)(W.dev + o_qu);
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes, hipMemcpyHostToDevice, S), "H2D genotype assignment") ||
-            !ok(h, launch_assign(p, n_c, S), "phmm_assign_kernel") ||
-            !ok(h, hipMemcpyAsync(W.host + o_gp, W.dev + o_gp, total - o_gp, hipMemcpyDeviceToHost, S), "D2H genotype assignment") ||
-            !ok(h, hipStreamSynchronize(S), "sync(genotype assignment)"))
+        p.out_off = W.dev_ptr(s_oo);
+        p.sub_pl = W.dev_ptr(s_sp);
+        p.gp = W.dev_ptr(s_gp);
+        p.pg = W.dev_ptr(s_pg);
+        p.gt = W.dev_ptr(s_gt);
+        p.gq = W.dev_ptr(s_gq);
+        p.log10_gq = W.dev_ptr(s_lq);
+        p.called = W.dev_ptr(s_cl);
+        p.flags = W.dev_ptr(s_fl);
+        p.p_no_alt = W.dev_ptr(s_pna);
+        p.qual_update = W.dev_ptr(s_qu);
+        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D genotype assignment") ||
+            !hip_ok(h, launch_assign(p, n_c, S), "phmm_assign_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H genotype assignment") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(genotype assignment)"))
             return PHMM_ERR_HIP;
         for (uint32_t i = 0; i < n_c; ++i) {
             const uint32_t e = computed[i];
             const size_t n = (size_t)n_samples * c_Gn[i], from = c_out_off[i], es = (size_t)e * n_samples, is = (size_t)i * n_samples;
-            memcpy(sub_pl + sub_pl_off[e], W.host + o_sp + 4 * from, 4 * n);
+            memcpy(sub_pl + sub_pl_off[e], W.host_ptr(s_sp) + from, 4 * n);
             if (posteriors) {
-                memcpy(gp + sub_pl_off[e], W.host + o_gp + 8 * from, 8 * n);
-                memcpy(pg + sub_pl_off[e], W.host + o_pg + 8 * from, 8 * n);
-                log10_p_error_posterior[e] = ((const double *)(W.host + o_qu))[i];
+                memcpy(gp + sub_pl_off[e], W.host_ptr(s_gp) + from, 8 * n);
+                memcpy(pg + sub_pl_off[e], W.host_ptr(s_pg) + from, 8 * n);
+                log10_p_error_posterior[e] = W.host_ptr(s_qu)[i];
             }
-            memcpy(gt + es * ploidy, W.host + o_gt + 4 * is * ploidy, 4ull * n_samples * ploidy);
-            memcpy(gq + es, W.host + o_gq + 4 * is, 4ull * n_samples);
-            if (log10_gq) memcpy(log10_gq + es, W.host + o_lq + 8 * is, 8ull * n_samples);
-            memcpy(sample_called + es, W.host + o_cl + is, n_samples);
-            memcpy(sample_flags + es, W.host + o_fl + is, n_samples);
+            memcpy(gt + es * ploidy, W.host_ptr(s_gt) + is * ploidy, 4ull * n_samples * ploidy);
+            memcpy(gq + es, W.host_ptr(s_gq) + is, 4ull * n_samples);
+            if (log10_gq) memcpy(log10_gq + es, W.host_ptr(s_lq) + is, 8ull * n_samples);
+            memcpy(sample_called + es, W.host_ptr(s_cl) + is, n_samples);
+            memcpy(sample_flags + es, W.host_ptr(s_fl) + is, n_samples);
         }
         return PHMM_OK;
-    } catch (const std::bad_alloc &) {
-        h->err = "phmm_assign_genotypes: out of host memory";
-        return h->err_code = PHMM_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        h->err = std::string("phmm_assign_genotypes: ") + e.what();
-        return h->err_code = PHMM_ERR_INTERNAL;
-    }
+    PHMM_GUARD_END(h, "phmm_assign_genotypes", PHMM_FAIL_CODE)
 }
 
 }  // extern "C"

@@ -7,30 +7,13 @@
 
 #include "phmm_cigar_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 
 using namespace phmm;
 
+using namespace phmm_host;
+
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 int fail(phmm_handle *h, const char *msg) {
     h->err = std::string("phmm_project_to_reference: ") + msg;
@@ -49,8 +32,8 @@ extern "C" int phmm_project_to_reference(phmm_handle *h, uint32_t n_regions, con
                                          const uint64_t *out_cigar_off, uint32_t *out_cigar, uint32_t *n_out_cigar,
                                          int64_t *new_pos, int32_t *status) {
     if (!h) return PHMM_ERR_INVALID_ARG;
-    try {
-        phmm_host::latch_slot0(h);
+    PHMM_GUARD_BEGIN
+        latch_slot0(h);
         h->err_code = PHMM_OK;
         if (!n_regions) return PHMM_OK;
         if (!region_read_off || !region_hap_off || !region_ref_hap || !region_reference_start) return fail(h, "null array");
@@ -90,121 +73,89 @@ extern "C" int phmm_project_to_reference(phmm_handle *h, uint32_t n_regions, con
         const uint32_t capacity = 4 * (max_sw + max_hc + 2) + 8;
         (void)max_oc;
 
-        DevGuard dg(h->device);
-        phmm_handle::SwWork &W = h->swork;
+        DeviceGuard dg(h->device);
+        phmm_handle::SwWork &SW = h->swork;
+        StagingBuffer &W = SW.staging;
         hipStream_t S = h->streams[0];
         // ---- staging: inputs, then [flags | status | n_out | new_pos | out cigar] ----------------------------------------
-        size_t o = 0;
-        auto place = [&](size_t bytes) {
-            const size_t at = o;
-            o += up256(bytes);
-            return at;
-        };
-        const size_t o_rro = place(4ull * (n_regions + 1)), o_rho = place(4ull * (n_regions + 1)), o_ro = place(4ull * (n_reads + 1)),
-                     o_rb = place(rb), o_ho = place(4ull * (n_haps + 1)), o_hb = place(hb), o_rrh = place(4ull * n_regions),
-                     o_rs = place(8ull * n_regions), o_hco = place(4ull * (n_haps + 1)), o_hc = place(4ull * n_hc), o_hs = place(4ull * n_haps),
-                     o_ba = place(4ull * n_reads), o_swo = place(8ull * (n_reads + 1)), o_sw = place(4ull * n_sw), o_nsw = place(4ull * n_reads),
-                     o_so = place(4ull * n_reads), o_oco = place(4ull * (n_reads + 1)), o_oc = place(4ull * n_oc), o_oo = place(8ull * (n_reads + 1)),
-                     in_bytes = o;
-        const size_t o_fl = place(256), o_st = place(4ull * n_reads), o_no = place(4ull * n_reads), o_np = place(8ull * n_reads),
-                     o_out = place(4ull * n_out), total = o;
-        if (W.cap < total) {
-            for (int i = 0; i < 3; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (W.dev) (void)hipFree(W.dev);
-            if (W.host) (void)hipHostFree(W.host);
-            W.dev = W.host = W.host_dev = nullptr;
-            W.cap = 0;
-            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(project staging)") ||
-                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(project staging)"))
-                return PHMM_ERR_HIP;
-            W.cap = cap;
-        }
+        StageLayout L;
+        const auto s_rro = L.in(region_read_off, n_regions + 1), s_rho = L.in(region_hap_off, n_regions + 1), s_ro = L.in(read_off, n_reads + 1);
+        const auto s_rb = L.in(read_bases, rb);
+        const auto s_ho = L.in(hap_off, n_haps + 1);
+        const auto s_hb = L.in(hap_bases, hb);
+        const auto s_rrh = L.in(region_ref_hap, n_regions);
+        const auto s_rs = L.in(region_reference_start, n_regions);
+        const auto s_hco = L.in(hap_cigar_off, n_haps + 1), s_hc = L.in(hap_cigar, n_hc), s_hs = L.in(hap_start_wrt_ref, n_haps);
+        const auto s_ba = L.in(best_allele, n_reads);
+        const auto s_swo = L.in(sw_cigar_off, n_reads + 1);
+        const auto s_sw = L.in(sw_cigar, n_sw), s_nsw = L.in(n_sw_cigar, n_reads);
+        const auto s_so = L.in(sw_offset, n_reads);
+        const auto s_oco = L.in(orig_cigar_off, n_reads + 1), s_oc = L.in(orig_cigar, n_oc);
+        const auto s_oo = L.in(out_cigar_off, n_reads + 1);
+        L.end_inputs();
+        const auto s_fl = L.out<uint32_t>(64);  // zeroed below; travels to the device with the inputs
+        const auto s_st = L.out<int32_t>(n_reads);
+        const auto s_no = L.out<uint32_t>(n_reads);
+        const auto s_np = L.out<int64_t>(n_reads);
+        const auto s_out = L.out<uint32_t>(n_out);
+        if (!W.reserve(h, L, "project staging")) return PHMM_ERR_HIP;
+        memset(W.host_ptr(s_fl), 0, 256);
         const size_t ws_bytes = (size_t)n_reads * 4 * capacity * 4;  // the lanes' builders live in the Smith-Waterman slab
-        if (W.slab_bytes < ws_bytes) {
+        if (SW.slab_bytes < ws_bytes) {
             (void)hipStreamSynchronize(S);
-            if (W.slab) (void)hipFree(W.slab);
-            W.slab = nullptr;
-            W.slab_bytes = 0;
-            if (!ok(h, hipMalloc((void **)&W.slab, ws_bytes), "hipMalloc(project workspace)")) return PHMM_ERR_HIP;
-            W.slab_bytes = ws_bytes;
+            if (SW.slab) (void)hipFree(SW.slab);
+            SW.slab = nullptr;
+            SW.slab_bytes = 0;
+            if (!hip_ok(h, hipMalloc((void **)&SW.slab, ws_bytes), "hipMalloc(project workspace)")) return PHMM_ERR_HIP;
+            SW.slab_bytes = ws_bytes;
         }
-        auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
-        };
-        put(o_rro, region_read_off, 4ull * (n_regions + 1));
-        put(o_rho, region_hap_off, 4ull * (n_regions + 1));
-        put(o_ro, read_off, 4ull * (n_reads + 1));
-        put(o_rb, read_bases, rb);
-        put(o_ho, hap_off, 4ull * (n_haps + 1));
-        put(o_hb, hap_bases, hb);
-        put(o_rrh, region_ref_hap, 4ull * n_regions);
-        put(o_rs, region_reference_start, 8ull * n_regions);
-        put(o_hco, hap_cigar_off, 4ull * (n_haps + 1));
-        put(o_hc, hap_cigar, 4ull * n_hc);
-        put(o_hs, hap_start_wrt_ref, 4ull * n_haps);
-        put(o_ba, best_allele, 4ull * n_reads);
-        put(o_swo, sw_cigar_off, 8ull * (n_reads + 1));
-        put(o_sw, sw_cigar, 4ull * n_sw);
-        put(o_nsw, n_sw_cigar, 4ull * n_reads);
-        put(o_so, sw_offset, 4ull * n_reads);
-        put(o_oco, orig_cigar_off, 4ull * (n_reads + 1));
-        put(o_oc, orig_cigar, 4ull * n_oc);
-        put(o_oo, out_cigar_off, 8ull * (n_reads + 1));
-        memset(W.host + o_fl, 0, 256);
         ProjectParams p{};
         p.n_reads = n_reads;
         p.n_regions = n_regions;
-        p.region_read_off = (const uint32_t *)(W.dev + o_rro);
-        p.region_hap_off = (const uint32_t *)(W.dev + o_rho);
-        p.read_off = (const uint32_t *)(W.dev + o_ro);
-        p.read_bases = (const uint8_t *)(W.dev + o_rb);
-        p.hap_off = (const uint32_t *)(W.dev + o_ho);
-        p.hap_bases = (const uint8_t *)(W.dev + o_hb);
-        p.region_ref_hap = (const int32_t *)(W.dev + o_rrh);
-        p.region_reference_start = (const uint64_t *)(W.dev + o_rs);
-        p.hap_cigar_off = (const uint32_t *)(W.dev + o_hco);
-        p.hap_cigar = (const uint32_t *)(W.dev + o_hc);
-        p.hap_start_wrt_ref = (const uint32_t *)(W.dev + o_hs);
-        p.best_allele = (const int32_t *)(W.dev + o_ba);
-        p.sw_cigar_off = (const uint64_t *)(W.dev + o_swo);
-        p.sw_cigar = (const uint32_t *)(W.dev + o_sw);
-        p.n_sw_cigar = (const uint32_t *)(W.dev + o_nsw);
-        p.sw_offset = (const int32_t *)(W.dev + o_so);
-        p.orig_cigar_off = (const uint32_t *)(W.dev + o_oco);
-        p.orig_cigar = (const uint32_t *)(W.dev + o_oc);
-        p.out_cigar_off = (const uint64_t *)(W.dev + o_oo);
-        p.out_cigar = (uint32_t *)(W.dev + o_out);
-        p.n_out_cigar = (uint32_t *)(W.dev + o_no);
-        p.new_pos = (int64_t *)(W.dev + o_np);
-        p.status = (int32_t *)(W.dev + o_st);
-        p.flags = (uint32_t *)(W.dev + o_fl);
-        p.workspace = W.slab;
+        p.region_read_off = W.dev_ptr(s_rro);
+        p.region_hap_off = W.dev_ptr(s_rho);
+        p.read_off = W.dev_ptr(s_ro);
+        p.read_bases = W.dev_ptr(s_rb);
+        p.hap_off = W.dev_ptr(s_ho);
+        p.hap_bases = W.dev_ptr(s_hb);
+        p.region_ref_hap = W.dev_ptr(s_rrh);
+        p.region_reference_start = W.dev_ptr(s_rs);
+        p.hap_cigar_off = W.dev_ptr(s_hco);
+        p.hap_cigar = W.dev_ptr(s_hc);
+        p.hap_start_wrt_ref = W.dev_ptr(s_hs);
+        p.best_allele = W.dev_ptr(s_ba);
+        p.sw_cigar_off = W.dev_ptr(s_swo);
+        p.sw_cigar = W.dev_ptr(s_sw);
+        p.n_sw_cigar = W.dev_ptr(s_nsw);
+        p.sw_offset = W.dev_ptr(s_so);
+        p.orig_cigar_off = W.dev_ptr(s_oco);
+        p.orig_cigar = W.dev_ptr(s_oc);
+        p.out_cigar_off = W.dev_ptr(s_oo);
+        p.out_cigar = W.dev_ptr(s_out);
+        p.n_out_cigar = W.dev_ptr(s_no);
+        p.new_pos = W.dev_ptr(s_np);
+        p.status = W.dev_ptr(s_st);
+        p.flags = W.dev_ptr(s_fl);
+        p.workspace = SW.slab;
         p.capacity = capacity;
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes + 256, hipMemcpyHostToDevice, S), "H2D project") ||
-            !ok(h, launch_project(p, S), "phmm_project_kernel") ||
-            !ok(h, hipMemcpyAsync(W.host + o_fl, W.dev + o_fl, total - o_fl, hipMemcpyDeviceToHost, S), "D2H project") ||
-            !ok(h, hipStreamSynchronize(S), "sync(project)"))
+        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes + 256, hipMemcpyHostToDevice, S), "H2D project") ||
+            !hip_ok(h, launch_project(p, S), "phmm_project_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H project") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(project)"))
             return PHMM_ERR_HIP;
-        memcpy(status, W.host + o_st, 4ull * n_reads);
-        memcpy(n_out_cigar, W.host + o_no, 4ull * n_reads);
-        memcpy(new_pos, W.host + o_np, 8ull * n_reads);
+        memcpy(status, W.host_ptr(s_st), 4ull * n_reads);
+        memcpy(n_out_cigar, W.host_ptr(s_no), 4ull * n_reads);
+        memcpy(new_pos, W.host_ptr(s_np), 8ull * n_reads);
         // only what the call reports: a slot's words behind the read's elements, and the slots of reads that are not
         // realigned, stay as the caller left them (the kernel wrote nothing there: the staging holds older calls' bytes)
         for (uint32_t r = 0; r < n_reads; ++r) {
             const uint64_t n = std::min<uint64_t>(n_out_cigar[r], out_cigar_off[r + 1] - out_cigar_off[r]);
-            if (status[r] == CIGAR_OK && n) memcpy(out_cigar + out_cigar_off[r], W.host + o_out + 4ull * out_cigar_off[r], 4ull * n);
+            if (status[r] == CIGAR_OK && n) memcpy(out_cigar + out_cigar_off[r], W.host_ptr(s_out) + out_cigar_off[r], 4ull * n);
         }
-        if (*(const uint32_t *)(W.host + o_fl) & 1u) {
+        if (*W.host_ptr(s_fl) & 1u) {
             h->err = "phmm_project_to_reference: a CIGAR needs more elements than its slot holds (n_out_cigar has the sizes)";
             return h->err_code = PHMM_ERR_CIGAR_CAPACITY;
         }
         return PHMM_OK;
-    } catch (const std::bad_alloc &) {
-        h->err = "phmm_project_to_reference: out of host memory";
-        return h->err_code = PHMM_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        h->err = std::string("phmm_project_to_reference: ") + e.what();
-        return h->err_code = PHMM_ERR_INTERNAL;
-    }
+    PHMM_GUARD_END(h, "phmm_project_to_reference", PHMM_FAIL_CODE)
 }

@@ -8,31 +8,14 @@
 
 #include "phmm_genotype_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 #include "phmm_tables.hpp"
 
 using namespace phmm;
 
+using namespace phmm_host;
+
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 int fail(phmm_handle *h, const std::string &msg) {
     h->err = "phmm_genotype_likelihoods: " + msg;
@@ -120,7 +103,7 @@ int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t
                               const int64_t *event_start, const int64_t *event_end, const int32_t *event_hap_allele,
                               const uint64_t *gl_off, double *gl, int32_t *pl, uint32_t *n_evidence) {
     if (!h) return PHMM_ERR_INVALID_ARG;
-    try {
+    PHMM_GUARD_BEGIN
         h->err_code = PHMM_OK;
         if (!n_events) return PHMM_OK;
         // ---- arguments: everything is checked before anything is written ----------------------------------------------------
@@ -166,132 +149,88 @@ int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t
             region_used[g] = 1;
             max_alleles = std::max(max_alleles, A);
         }
-        std::vector<uint64_t> lk_off(n_regions, 0);
-        uint64_t n_lk = 0;
-        for (uint32_t g = 0; g < n_regions; ++g) {
-            if (!region_used[g]) continue;
-            lk_off[g] = n_lk;
-            n_lk += (uint64_t)(region_read_off[g + 1] - region_read_off[g]) * (region_hap_off[g + 1] - region_hap_off[g]);
-        }
+        const LikelihoodGather lks(n_regions, region_read_off, region_hap_off, region_used);
 
         // ---- the genotypes of (ploidy, most alleles): the index order of fewer alleles is a prefix of it ------------------
         const auto &T = genotype_table_of(h, ploidy, max_alleles);
         std::vector<double> log10_k(ploidy + 1, 0.0);
         for (uint32_t k = 1; k <= ploidy; ++k) log10_k[k] = std::log10((double)k);
 
-        DevGuard dg(h->device);
-        phmm_handle::GtWork &W = h->gwork;
+        DeviceGuard dg(h->device);
+        StagingBuffer &W = h->gwork.staging;
         hipStream_t S = h->streams[0];
-        if (!W.d_jacobian) {
+        if (!h->gwork.d_jacobian) {
             const auto &jac = table_jacobian();
-            if (!ok(h, hipMalloc((void **)&W.d_jacobian, jac.size() * sizeof(double)), "hipMalloc(jacobian)") ||
-                !ok(h, hipMemcpy(W.d_jacobian, jac.data(), jac.size() * sizeof(double), hipMemcpyHostToDevice), "copy jacobian")) {
-                if (W.d_jacobian) (void)hipFree(W.d_jacobian);
-                W.d_jacobian = nullptr;
+            double *&d_jac = h->gwork.d_jacobian;
+            if (!hip_ok(h, hipMalloc((void **)&d_jac, jac.size() * sizeof(double)), "hipMalloc(jacobian)") ||
+                !hip_ok(h, hipMemcpy(d_jac, jac.data(), jac.size() * sizeof(double), hipMemcpyHostToDevice), "copy jacobian")) {
+                if (d_jac) (void)hipFree(d_jac);
+                d_jac = nullptr;
                 return PHMM_ERR_HIP;
             }
         }
         // ---- staging: inputs, then [gl | pl | n_evidence] ---------------------------------------------------------------------
-        size_t o = 0;
-        auto place = [&](size_t bytes) {
-            const size_t at = o;
-            o += up256(bytes);
-            return at;
-        };
-        const size_t n_gt = T.first.size() - 1;
-        const size_t o_rro = place(4ull * (n_regions + 1)), o_rho = place(4ull * (n_regions + 1)), o_lko = place(8ull * n_regions),
-                     o_lk = place(8ull * n_lk), o_kp = place(n_reads), o_rs = place(4ull * n_reads), o_st = place(8ull * n_reads),
-                     o_en = place(8ull * n_reads), o_er = place(4ull * n_events), o_eao = place(4ull * (n_events + 1)),
-                     o_emo = place(4ull * n_events), o_map = place(4ull * n_map), o_es = place(8ull * n_events), o_ee = place(8ull * n_events),
-                     o_eoo = place(8ull * n_events), o_gc = place(4ull * n_events), o_co = place(4ull * (n_gt + 1)),
-                     o_c = place(4ull * T.second.size()), o_l10 = place(8ull * (ploidy + 1)), in_bytes = o;
-        const size_t o_gl = place(8ull * n_out), o_pl = place(4ull * n_out), o_ne = place(4ull * n_events * n_samples), total = o;
-        if (W.cap < total) {
-            (void)hipStreamSynchronize(S);
-            if (W.dev) (void)hipFree(W.dev);
-            if (W.host) (void)hipHostFree(W.host);
-            W.dev = W.host = nullptr;
-            W.cap = 0;
-            const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-            if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(genotype staging)") ||
-                !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(genotype staging)"))
-                return PHMM_ERR_HIP;
-            W.cap = cap;
-        }
-        auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
-        };
-        put(o_rro, region_read_off, 4ull * (n_regions + 1));
-        put(o_rho, region_hap_off, 4ull * (n_regions + 1));
-        put(o_lko, lk_off.data(), 8ull * n_regions);
-        for (uint32_t g = 0; g < n_regions; ++g)
-            if (region_used[g])
-                put(o_lk + 8 * lk_off[g], likelihoods + out_off[g],
-                    8ull * (region_read_off[g + 1] - region_read_off[g]) * (region_hap_off[g + 1] - region_hap_off[g]));
-        if (keep) put(o_kp, keep, n_reads);
-        else if (n_reads) memset(W.host + o_kp, 1, n_reads);
-        put(o_rs, read_sample, 4ull * n_reads);
-        put(o_st, read_start, 8ull * n_reads);
-        put(o_en, read_end, 8ull * n_reads);
-        put(o_er, event_region, 4ull * n_events);
-        put(o_eao, event_allele_off, 4ull * (n_events + 1));
-        put(o_emo, map_off.data(), 4ull * n_events);
-        put(o_map, event_hap_allele, 4ull * n_map);
-        put(o_es, event_start, 8ull * n_events);
-        put(o_ee, event_end, 8ull * n_events);
-        put(o_eoo, out_dense.data(), 8ull * n_events);
-        put(o_gc, G.data(), 4ull * n_events);
-        put(o_co, T.first.data(), 4ull * (n_gt + 1));
-        put(o_c, T.second.data(), 4ull * T.second.size());
-        put(o_l10, log10_k.data(), 8ull * (ploidy + 1));
-        h->stat_staged_bytes += in_bytes;
+        StageLayout L;
+        const auto s_rro = L.in(region_read_off, n_regions + 1), s_rho = L.in(region_hap_off, n_regions + 1);
+        const auto s_lko = L.in(lks.off.data(), n_regions);
+        const auto s_lk = L.in<double>(lks.n);
+        const auto s_kp = L.in<uint8_t>(n_reads);
+        const auto s_rs = L.in(read_sample, n_reads);
+        const auto s_st = L.in(read_start, n_reads), s_en = L.in(read_end, n_reads);
+        const auto s_er = L.in(event_region, n_events), s_eao = L.in(event_allele_off, n_events + 1), s_emo = L.in(map_off.data(), n_events);
+        const auto s_map = L.in(event_hap_allele, n_map);
+        const auto s_es = L.in(event_start, n_events), s_ee = L.in(event_end, n_events);
+        const auto s_eoo = L.in(out_dense.data(), n_events);
+        const auto s_gc = L.in(G.data(), n_events), s_co = L.in(T.first.data(), T.first.size()), s_c = L.in(T.second.data(), T.second.size());
+        const auto s_l10 = L.in(log10_k.data(), ploidy + 1);
+        L.end_inputs();
+        const auto s_gl = L.out<double>(n_out);
+        const auto s_pl = L.out<int32_t>(n_out);
+        const auto s_ne = L.out<uint32_t>((size_t)n_events * n_samples);
+        if (!W.reserve(h, L, "genotype staging")) return PHMM_ERR_HIP;
+        lks.into(W.host_ptr(s_lk), W.host_ptr(s_kp), out_off, likelihoods, keep);
+        h->stat_staged_bytes += L.in_bytes;
 
         GenotypeParams p{};
         p.n_events = n_events;
         p.n_samples = n_samples;
         p.ploidy = ploidy;
-        p.region_read_off = (const uint32_t *)(W.dev + o_rro);
-        p.region_hap_off = (const uint32_t *)(W.dev + o_rho);
-        p.region_lk_off = (const uint64_t *)(W.dev + o_lko);
-        p.likelihoods = (const double *)(W.dev + o_lk);
-        p.keep = (const uint8_t *)(W.dev + o_kp);
-        p.read_sample = (const uint32_t *)(W.dev + o_rs);
-        p.read_start = (const int64_t *)(W.dev + o_st);
-        p.read_end = (const int64_t *)(W.dev + o_en);
-        p.event_region = (const uint32_t *)(W.dev + o_er);
-        p.event_allele_off = (const uint32_t *)(W.dev + o_eao);
-        p.event_map_off = (const uint32_t *)(W.dev + o_emo);
-        p.event_hap_allele = (const int32_t *)(W.dev + o_map);
-        p.event_start = (const int64_t *)(W.dev + o_es);
-        p.event_end = (const int64_t *)(W.dev + o_ee);
-        p.event_out_off = (const uint64_t *)(W.dev + o_eoo);
-        p.genotype_count = (const uint32_t *)(W.dev + o_gc);
-        p.gt_comp_off = (const uint32_t *)(W.dev + o_co);
-        p.gt_comp = (const uint32_t *)(W.dev + o_c);
-        p.log10_k = (const double *)(W.dev + o_l10);
-        p.jacobian = W.d_jacobian;
-        p.gl = (double *)(W.dev + o_gl);
-        p.pl = (int32_t *)(W.dev + o_pl);
-        p.n_evidence = (uint32_t *)(W.dev + o_ne);
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, in_bytes, hipMemcpyHostToDevice, S), "H2D genotype") ||
-            !ok(h, launch_genotype(p, S), "phmm_genotype_kernel") ||
-            !ok(h, hipMemcpyAsync(W.host + o_gl, W.dev + o_gl, total - o_gl, hipMemcpyDeviceToHost, S), "D2H genotype") ||
-            !ok(h, hipStreamSynchronize(S), "sync(genotype)"))
+        p.region_read_off = W.dev_ptr(s_rro);
+        p.region_hap_off = W.dev_ptr(s_rho);
+        p.region_lk_off = W.dev_ptr(s_lko);
+        p.likelihoods = W.dev_ptr(s_lk);
+        p.keep = W.dev_ptr(s_kp);
+        p.read_sample = W.dev_ptr(s_rs);
+        p.read_start = W.dev_ptr(s_st);
+        p.read_end = W.dev_ptr(s_en);
+        p.event_region = W.dev_ptr(s_er);
+        p.event_allele_off = W.dev_ptr(s_eao);
+        p.event_map_off = W.dev_ptr(s_emo);
+        p.event_hap_allele = W.dev_ptr(s_map);
+        p.event_start = W.dev_ptr(s_es);
+        p.event_end = W.dev_ptr(s_ee);
+        p.event_out_off = W.dev_ptr(s_eoo);
+        p.genotype_count = W.dev_ptr(s_gc);
+        p.gt_comp_off = W.dev_ptr(s_co);
+        p.gt_comp = W.dev_ptr(s_c);
+        p.log10_k = W.dev_ptr(s_l10);
+        p.jacobian = h->gwork.d_jacobian;
+        p.gl = W.dev_ptr(s_gl);
+        p.pl = W.dev_ptr(s_pl);
+        p.n_evidence = W.dev_ptr(s_ne);
+        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D genotype") ||
+            !hip_ok(h, launch_genotype(p, S), "phmm_genotype_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H genotype") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(genotype)"))
             return PHMM_ERR_HIP;
         for (uint32_t e = 0; e < n_events; ++e) {
             const size_t n = (size_t)n_samples * G[e];
-            memcpy(gl + gl_off[e], W.host + o_gl + 8 * out_dense[e], 8 * n);
-            if (pl) memcpy(pl + gl_off[e], W.host + o_pl + 4 * out_dense[e], 4 * n);
+            memcpy(gl + gl_off[e], W.host_ptr(s_gl) + out_dense[e], 8 * n);
+            if (pl) memcpy(pl + gl_off[e], W.host_ptr(s_pl) + out_dense[e], 4 * n);
         }
-        if (n_evidence) memcpy(n_evidence, W.host + o_ne, 4ull * n_events * n_samples);
+        if (n_evidence) memcpy(n_evidence, W.host_ptr(s_ne), 4ull * n_events * n_samples);
         return PHMM_OK;
-    } catch (const std::bad_alloc &) {
-        h->err = "phmm_genotype_likelihoods: out of host memory";
-        return h->err_code = PHMM_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        h->err = std::string("phmm_genotype_likelihoods: ") + e.what();
-        return h->err_code = PHMM_ERR_INTERNAL;
-    }
+    PHMM_GUARD_END(h, "phmm_genotype_likelihoods", PHMM_FAIL_CODE)
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Private to the host side of libphmm.so (phmm_api.cpp, phmm_submit.cpp): the engine handle, its staging arenas and the
-// two internal entry points the cross-thread queue builds on.  Nothing here is part of the ABI (include/phmm.h).
+// Private to the host side of libphmm.so (every .cpp of it): the engine handle, its staging arenas and buffers, and what the
+// host files call of one another.  Nothing here is part of the ABI (include/phmm.h).
 #pragma once
 #include "../../include/phmm.h"
 
@@ -26,6 +26,32 @@ struct Arena {
     // staged when the call ends -- a device store that lands in the pinned mirror after (or outside) its call fails loudly
     size_t canary_off = 0, canary_bytes = 0;
     std::vector<unsigned char> canary_inputs;
+};
+
+// Grow-only device buffer with a pinned host mirror at identical offsets, for the entry points that stage their arrays
+// themselves.  A call lays its arrays out with a StageLayout (phmm_staging.hpp, where the member functions are too).
+namespace phmm_host {
+class StageLayout;
+}
+template <class T>
+struct StageSlot {  // `count` elements of T at byte offset `off` of the buffer and of its mirror
+    size_t off = 0, count = 0;
+};
+struct StagingBuffer {
+    char *dev = nullptr, *host = nullptr;
+    char *host_dev = nullptr;  // the mirror as the device sees it: null until a caller asks for it (the aligner's small calls)
+    size_t cap = 0;
+    bool grow(phmm_handle *h, size_t total, const char *owner);
+    bool reserve(phmm_handle *h, const phmm_host::StageLayout &L, const char *owner);
+    void release();  // (phmm_destroy)
+    template <class T>
+    T *dev_ptr(StageSlot<T> s) const {
+        return (T *)(dev + s.off);
+    }
+    template <class T>
+    T *host_ptr(StageSlot<T> s) const {
+        return (T *)(host + s.off);
+    }
 };
 
 // Developer switches: read from the PHMM_* environment variables ONCE, in phmm_create, and
@@ -93,9 +119,7 @@ struct phmm_handle {
     int err_code = PHMM_OK;  // status of the last failure (set together with err)
     Switches sw;
     struct SwWork {  // phmm_sw_align (phmm_sw.cpp): grow-only staging and backtrack slabs
-        char *dev = nullptr, *host = nullptr;
-        char *host_dev = nullptr;  // the pinned mirror as the device sees it (small calls: kernels store their results there)
-        size_t cap = 0;
+        StagingBuffer staging;  // (small calls: kernels store their results into its mirror, host_dev)
         uint32_t *slab = nullptr;
         size_t slab_bytes = 0;
         uint32_t *ws = nullptr;  // the projection's builders (phmm_realign_reads)
@@ -127,24 +151,13 @@ struct phmm_handle {
         std::unordered_map<uint64_t, int> blocks_per_cu;  // by (lanes, columns, LDS bytes): asked of the runtime once
     } swork;
     struct GtWork {  // phmm_genotype_likelihoods (phmm_genotype.cpp): grow-only staging, the resident Jacobian table
-        char *dev = nullptr, *host = nullptr;
-        size_t cap = 0;
+        StagingBuffer staging;
         double *d_jacobian = nullptr;  // JacobianLogTable, uploaded by the handle's first call
         // the genotypes of (ploidy, alleles) in index order, by (ploidy << 32 | alleles): [G + 1] offsets, (allele | count << 16)
         std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
     } gwork;
-    struct AfWork {  // phmm_allele_frequency (phmm_af.cpp): grow-only staging
-        char *dev = nullptr, *host = nullptr;
-        size_t cap = 0;
-    } afwork;
-    struct AnnWork {  // phmm_annotate_events (phmm_annotate.cpp): grow-only staging
-        char *dev = nullptr, *host = nullptr;
-        size_t cap = 0;
-    } annwork;
-    struct AsWork {  // phmm_assign_genotypes (phmm_assign.cpp): grow-only staging
-        char *dev = nullptr, *host = nullptr;
-        size_t cap = 0;
-    } aswork;
+    // grow-only staging of phmm_allele_frequency (phmm_af.cpp), phmm_annotate_events (phmm_annotate.cpp), phmm_assign_genotypes (phmm_assign.cpp)
+    StagingBuffer af_staging, annotate_staging, assign_staging;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

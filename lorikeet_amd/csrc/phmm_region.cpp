@@ -24,30 +24,13 @@
 #include "phmm_cigar_internal.hpp"
 #include "phmm_host.hpp"
 #include "phmm_region_internal.hpp"
+#include "phmm_staging.hpp"
 #include "phmm_sw_internal.hpp"
 
 using namespace phmm;
 using namespace phmm_host;
 
 namespace {
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 struct PendingRegion {
     phmm_batch *b = nullptr;
@@ -141,14 +124,14 @@ bool ensure_sw_buffers(phmm_handle *h, size_t slab_bytes, size_t ws_bytes) {
         if (W.slab) (void)hipFree(W.slab);
         W.slab = nullptr;
         W.slab_bytes = 0;
-        if (!ok(h, hipMalloc((void **)&W.slab, slab_bytes), "hipMalloc(sw backtrack)")) return false;
+        if (!hip_ok(h, hipMalloc((void **)&W.slab, slab_bytes), "hipMalloc(sw backtrack)")) return false;
         W.slab_bytes = slab_bytes;
     }
     if (W.ws_bytes < ws_bytes) {
         if (W.ws) (void)hipFree(W.ws);
         W.ws = nullptr;
         W.ws_bytes = 0;
-        if (!ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(project workspace)")) return false;
+        if (!hip_ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(project workspace)")) return false;
         W.ws_bytes = ws_bytes;
     }
     return true;
@@ -196,7 +179,7 @@ bool queues_acquire(phmm_handle *h) {
             return false;
         }
         if ((size_t)(k / 4) >= P.batches.size()) {
-            DevGuard on_device(h->device);  // (hipExtStreamCreateWithCUMask creates on the calling thread's current device)
+            DeviceGuard on_device(h->device);  // (hipExtStreamCreateWithCUMask creates on the calling thread's current device)
             int cus = 0;
             (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
             const uint32_t words = (uint32_t)std::min(32, std::max(1, (cus + 31) / 32));
@@ -242,7 +225,7 @@ bool halves_acquire(phmm_handle *h) {
     QueuePool &P = g_queue_pool[h->device % kMaxDevices];
     std::lock_guard<std::mutex> lk(P.mu);
     if (P.halves_pairs >= kHalvesPairs) return false;
-    DevGuard on_device(h->device);
+    DeviceGuard on_device(h->device);
     uint32_t mask_a[32], mask_b[32];
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
@@ -283,7 +266,7 @@ void latch_slot0(phmm_handle *h) {
         // THREAD's current device: a worker thread of phmm_*_compute_multi, or a rayon thread of hip_backend.rs, is on device 0
         // whatever the handle's -- the pool's streams must belong to the device they are filed under)
         if (h->swork.queue_index == -1) {
-            DevGuard dg(h->device);
+            DeviceGuard dg(h->device);
             own = queues_acquire(h);
         } else {
             own = h->swork.queue_index >= 0;
@@ -445,7 +428,7 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
     // (the last kernel of a small call reports to the calling thread through the mirror: region_finish)
     const bool flag_wait = mirror && !chained && nr && h->sw.region_flag_wait;
     if ((pair_stride || flag_wait) && !W.d_pair_done) {
-        if (!ok(h, hipMalloc((void **)&W.d_pair_done, 256), "hipMalloc") || !ok(h, hipMemset(W.d_pair_done, 0, 256), "hipMemset")) return bail(PHMM_ERR_HIP);
+        if (!hip_ok(h, hipMalloc((void **)&W.d_pair_done, 256), "hipMalloc") || !hip_ok(h, hipMemset(W.d_pair_done, 0, 256), "hipMemset")) return bail(PHMM_ERR_HIP);
         W.pair_done_target = 0;
         W.finish_count = 0;
     }
@@ -457,8 +440,8 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
         good = true;
     } else {
         batch_set_status(b, (uint32_t *)(A.dev + L.res));
-        good = ok(h, hipMemcpyAsync(A.dev, A.host, L.in_end, hipMemcpyHostToDevice, S), "H2D batch") &&
-               ok(h, hipMemsetAsync(A.dev + L.res, 0, 256, S), "memset status");
+        good = hip_ok(h, hipMemcpyAsync(A.dev, A.host, L.in_end, hipMemcpyHostToDevice, S), "H2D batch") &&
+               hip_ok(h, hipMemsetAsync(A.dev + L.res, 0, 256, S), "memset status");
     }
     // ---- the aligner, every read against every haplotype of its region: beside everything below, straight from the mirror ------
     auto sw_params = [&](const char *in_base) {
@@ -507,7 +490,7 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
         // -- enqueued right behind the PairHMM kernel -- waits for the count: an event that is still pending reaches the other
         // queue ~12 us late, one that has fired still costs ~6 us of barrier packet)
         sp.done_counter = W.d_pair_done;
-        good = ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, sp, (uint32_t)workers, G.lds, T_all), "phmm_sw_align_kernel (all pairs)");
+        good = hip_ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, sp, (uint32_t)workers, G.lds, T_all), "phmm_sw_align_kernel (all pairs)");
         if (good) {
             W.pair_done_target += (uint32_t)workers;  // (only what was launched is waited for)
             W.region_sw_all_calls += 1;
@@ -551,7 +534,7 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
             h->err = who + ": read too long for the pre-step kernel";
             return bail(PHMM_ERR_INVALID_ARG);
         }
-        good = ok(h, launch_prep(pp, S), "phmm_prep_reads");
+        good = hip_ok(h, launch_prep(pp, S), "phmm_prep_reads");
     }
     // ---- PairHMM ---------------------------------------------------------------------------------------------------------
     // The exact pass below -600 rides in-stream -- unless no pair of this batch can get there: every likelihood is at least
@@ -603,7 +586,7 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
         bp.ref_index = (uint32_t *)(A.dev + L.refidx);
         pb.skip_single_allele = (a.rcfg.flags & PHMM_REGION_SKIP_SINGLE_ALLELE) ? 1u : 0u;
         pb.keep_final = mirror ? (uint8_t *)(mirror + L.keep) : nullptr;
-        if (!pair_stride) good = ok(h, launch_post_best(pb, S), "phmm_post_best_reads");  // (else: part of phmm_pick_reads, below)
+        if (!pair_stride) good = hip_ok(h, launch_post_best(pb, S), "phmm_post_best_reads");  // (else: part of phmm_pick_reads, below)
     }
     // ---- alignments to the best haplotypes and their projection onto the reference -----------------------------------------
     ProjectParams pj{};
@@ -657,13 +640,13 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
         pj.wait_target = all_pairs_behind_pick ? W.pair_done_target + (uint32_t)workers : W.pair_done_target;
         pj.wait_ticks = (uint32_t)std::min<uint64_t>(100ull * (uint64_t)std::max(1, h->sw.region_pick_timeout_us), 0xffffffffull);
         uint32_t blocks = 0;
-        good = ok(h, launch_pick(pb, pj, S, &blocks), "phmm_pick_reads");
+        good = hip_ok(h, launch_pick(pb, pj, S, &blocks), "phmm_pick_reads");
         if (good && pj.finish_counter) W.finish_count += blocks;  // (only blocks that were launched count themselves in)
         if (good && all_pairs_behind_pick) launch_all_pairs();
     } else if (good && align) {
         SwParams sp = sw_params(A.dev);
         // (chunks of one call follow each other through the handle's one slab and workspace)
-        if (chained && W.region_sw_pending) good = ok(h, hipStreamWaitEvent(S, W.region_sw_done, 0), "hipStreamWaitEvent");
+        if (chained && W.region_sw_pending) good = hip_ok(h, hipStreamWaitEvent(S, W.region_sw_done, 0), "hipStreamWaitEvent");
         // (reads against their haplotypes: the tags-only sweep first, the full instance over the alignments that met a gap;
         // the counter is a word of the status block that is staged as zeros with the inputs)
         // (a call that met gaps in more than three alignments of ten sends the handle's next fifteen straight to the full instance)
@@ -680,15 +663,15 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
             s2.todo = s1.todo_out;
             s2.todo_count = s1.todo_out_count;
             s2.feedback = (uint32_t *)(res_base + L.res + 192);
-            good = good && ok(h, launch_sw(G.L, G.K, G.transposed, SW_LITE, s1, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel (tags)") &&
-                   ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, s2, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel");
+            good = good && hip_ok(h, launch_sw(G.L, G.K, G.transposed, SW_LITE, s1, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel (tags)") &&
+                   hip_ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, s2, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel");
         } else {
-            good = good && ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, sp, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel");
+            good = good && hip_ok(h, launch_sw(G.L, G.K, G.transposed, G.variant, sp, (uint32_t)workers, G.lds, S), "phmm_sw_align_kernel");
         }
     } else if (good && nr) {  // nothing was aligned: the kernels behind the aligner still find defined alignments
         // (the projection below works in the handle's one workspace like every chunk's: behind the chunk before it)
-        if (chained && W.region_sw_pending) good = ok(h, hipStreamWaitEvent(S, W.region_sw_done, 0), "hipStreamWaitEvent");
-        good = good && ok(h, hipMemsetAsync(A.dev + L.nsw, 0, 4ull * nr, S), "memset") && ok(h, hipMemsetAsync(A.dev + L.swo, 0, 4ull * nr, S), "memset");
+        if (chained && W.region_sw_pending) good = hip_ok(h, hipStreamWaitEvent(S, W.region_sw_done, 0), "hipStreamWaitEvent");
+        good = good && hip_ok(h, hipMemsetAsync(A.dev + L.nsw, 0, 4ull * nr, S), "memset") && hip_ok(h, hipMemsetAsync(A.dev + L.swo, 0, 4ull * nr, S), "memset");
     }
     if (good && nr && !pair_stride) {
         if (!align && !ensure_sw_buffers(h, 0, (size_t)nr * 4ull * (4 * (sw_capacity + max_hap_cigar + 2) + 8) * 4ull)) return bail(PHMM_ERR_HIP);
@@ -697,17 +680,17 @@ int region_enqueue(phmm_handle *h, const RegionArgs &a, const std::vector<Region
             pj.capacity = 4 * (sw_capacity + max_hap_cigar + 2) + 8;
         }
         uint32_t blocks = 0;
-        good = ok(h, launch_project(pj, S, &blocks), "phmm_project_kernel");
+        good = hip_ok(h, launch_project(pj, S, &blocks), "phmm_project_kernel");
         if (good && pj.finish_counter) W.finish_count += blocks;  // (only blocks that were launched count themselves in)
         if (good && chained) {
-            if (!W.region_sw_done) good = ok(h, hipEventCreateWithFlags(&W.region_sw_done, hipEventDisableTiming), "hipEventCreate");
-            good = good && ok(h, hipEventRecord(W.region_sw_done, S), "hipEventRecord");
+            if (!W.region_sw_done) good = hip_ok(h, hipEventCreateWithFlags(&W.region_sw_done, hipEventDisableTiming), "hipEventCreate");
+            good = good && hip_ok(h, hipEventRecord(W.region_sw_done, S), "hipEventRecord");
             W.region_sw_pending = good;
         }
     }
     const bool eager = eager_d2h(h);  // otherwise region_finish fetches the results
     if (good && eager && !mirror)
-        good = ok(h, hipMemcpyAsync(A.host + L.res, A.dev + L.res, res_bytes, hipMemcpyDeviceToHost, S), "D2H results");
+        good = hip_ok(h, hipMemcpyAsync(A.host + L.res, A.dev + L.res, res_bytes, hipMemcpyDeviceToHost, S), "D2H results");
     if (!good) return bail(h->err_code ? h->err_code : PHMM_ERR_HIP);
     pending->b = b;
     pending->slot = h->slot;
@@ -761,9 +744,9 @@ int region_finish(phmm_handle *h, PendingRegion *p, uint32_t *sw_needed) {
             if (!told) __builtin_ia32_pause();
         }
     }
-    if ((!told && !ok(h, wait_stream(h, S), "sync")) ||
-        (p->d2h_pending && (!ok(h, hipMemcpyAsync(A.host + L.res, A.dev + L.res, L.end - L.res, hipMemcpyDeviceToHost, S), "D2H results") ||
-                            !ok(h, wait_stream(h, S), "sync(D2H)"))))
+    if ((!told && !hip_ok(h, wait_stream(h, S), "sync")) ||
+        (p->d2h_pending && (!hip_ok(h, hipMemcpyAsync(A.host + L.res, A.dev + L.res, L.end - L.res, hipMemcpyDeviceToHost, S), "D2H results") ||
+                            !hip_ok(h, wait_stream(h, S), "sync(D2H)"))))
         return done(PHMM_ERR_HIP);
     const char *hs = A.host;
     const uint32_t *sw_st = (const uint32_t *)(hs + L.res + 64);
@@ -772,7 +755,7 @@ int region_finish(phmm_handle *h, PendingRegion *p, uint32_t *sw_needed) {
         // hardware queue for both, an unmapped queue, a stalled device).  Let the aligner finish -- it writes into this call's
         // arena -- and hand nothing over: region_one_shot runs the call again as the chain, which needs no second queue.
         h->swork.region_pick_timeouts += 1;
-        const bool synced = ok(h, hipStreamSynchronize(S), "sync") && (!p->all_stream || ok(h, hipStreamSynchronize(p->all_stream), "sync(all pairs)"));
+        const bool synced = hip_ok(h, hipStreamSynchronize(S), "sync") && (!p->all_stream || hip_ok(h, hipStreamSynchronize(p->all_stream), "sync(all pairs)"));
         (void)canary_after_call(h, h->arenas[p->slot], L.res, L.end - L.res);
         return done(synced ? kPickTimedOut : PHMM_ERR_HIP);
     }
@@ -785,7 +768,7 @@ int region_finish(phmm_handle *h, PendingRegion *p, uint32_t *sw_needed) {
     }
     if (nr && sw_st[SW_STATUS_CAPACITY]) {  // (with every pair aligned: whichever pair's; the call goes round again the plain way)
         std::vector<uint32_t> n_sw(p->pair_stride ? (size_t)nr * p->pair_stride : nr);
-        if (!ok(h, hipMemcpy(n_sw.data(), A.dev + L.nsw, 4ull * n_sw.size(), hipMemcpyDeviceToHost), "D2H sw")) return done(PHMM_ERR_HIP);
+        if (!hip_ok(h, hipMemcpy(n_sw.data(), A.dev + L.nsw, 4ull * n_sw.size(), hipMemcpyDeviceToHost), "D2H sw")) return done(PHMM_ERR_HIP);
         if (sw_needed) *sw_needed = *std::max_element(n_sw.begin(), n_sw.end());
         h->err = "phmm_region_compute: a read -> haplotype CIGAR needs more elements than the library reserved";
         return done(PHMM_ERR_CIGAR_CAPACITY);
@@ -924,7 +907,7 @@ namespace phmm_host {
 // the regions of several submissions as ONE batch on `h` (a combined flush of phmm_region_submit): `combined` holds the
 // concatenated offset arrays and the shared configuration, payload and results are the parts'
 int region_compute_parts(phmm_handle *h, const RegionArgs &combined, const std::vector<RegionArgs> &parts) {
-    DevGuard dg(h->device);
+    DeviceGuard dg(h->device);
     if (!combined.region_read_off[combined.n_regions]) return PHMM_OK;
     uint32_t sw_capacity = kFirstSwCapacity;
     h->slot = 0;
@@ -932,7 +915,7 @@ int region_compute_parts(phmm_handle *h, const RegionArgs &combined, const std::
 }
 
 int region_compute(phmm_handle *h, const RegionArgs &a) {
-    DevGuard dg(h->device);
+    DeviceGuard dg(h->device);
     const uint32_t ng = a.n_regions, nr = a.region_read_off[ng];
     if (!nr) return PHMM_OK;  // no reads: no likelihoods, nothing to realign
     uint32_t sw_capacity = kFirstSwCapacity;

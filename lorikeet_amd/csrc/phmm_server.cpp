@@ -21,6 +21,7 @@
 
 #include "phmm_region_internal.hpp"
 #include "phmm_server.hpp"
+#include "phmm_staging.hpp"
 #include "phmm_tables.hpp"
 
 using namespace phmm;
@@ -36,17 +37,6 @@ constexpr int kServerStallMs = 5000;     // calls in flight and none finishing f
 constexpr uint32_t kSwCapacity = 24;      // CIGAR elements per read -> haplotype alignment (a call that needs more takes the launched pipeline)
 constexpr uint32_t kMaxHap = 512;          // 16 lanes x 25 columns per pair up to 400 bases, 32 x 16 beyond
 const int kSwKs[] = {2, 3, 4, 5, 6, 8};
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
 
 struct Slot {
     char *dev = nullptr, *host = nullptr, *host_dev = nullptr;  // host_dev: the mirror as the device sees it
@@ -102,7 +92,7 @@ struct Server {
 std::mutex g_mu;
 Server *g_servers[kMaxDevices] = {};
 
-bool hip_ok(hipError_t e) {
+bool quiet_ok(hipError_t e) {
     if (e == hipSuccess) return true;
     (void)hipGetLastError();
     return false;
@@ -110,23 +100,23 @@ bool hip_ok(hipError_t e) {
 
 // (g_mu held) everything a device's server owns but its slots; nullptr when the device refuses
 Server *server_create(int device) {
-    DevGuard dg(device);
+    DeviceGuard dg(device);
     Server *S = new Server();
     S->device = device;
     const int per_cu = server_blocks_per_cu();
     int cus = 0;
-    if (per_cu <= 0 || !hip_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device)) || cus <= 0) return S;
+    if (per_cu <= 0 || !quiet_ok(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device)) || cus <= 0) return S;
     S->n_blocks = (uint32_t)per_cu * (uint32_t)cus;
     // (the aligner's flags: one slab per worker wave, for the longest sweep the limits admit)
     S->slab_stride = (size_t)(std::max<uint32_t>(kMaxHap, SRV_MAX_ROWS) + 64) * (size_t)sw_flag_words(8) * 64;
     S->block_bytes = sizeof(SrvCtl) + 2 * sizeof(SrvMail) * SRV_MAIL;
     void *ring_dev = nullptr, *exit_dev = nullptr;
-    const bool good = hip_ok(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)) && hip_ok(hipMalloc((void **)&S->d_block, S->block_bytes)) &&
-                      hip_ok(hipMalloc((void **)&S->d_regions, sizeof(SrvRegion) * SRV_RING)) &&
-                      hip_ok(hipMalloc((void **)&S->d_slab, S->slab_stride * 4 * S->n_blocks)) &&
-                      hip_ok(hipHostMalloc((void **)&S->ring, sizeof(SrvEntry) * SRV_RING, hipHostMallocDefault)) &&
-                      hip_ok(hipHostMalloc((void **)&S->exit_word, 256, hipHostMallocDefault)) &&
-                      hip_ok(hipHostGetDevicePointer(&ring_dev, S->ring, 0)) && hip_ok(hipHostGetDevicePointer(&exit_dev, S->exit_word, 0));
+    const bool good = quiet_ok(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking)) && quiet_ok(hipMalloc((void **)&S->d_block, S->block_bytes)) &&
+                      quiet_ok(hipMalloc((void **)&S->d_regions, sizeof(SrvRegion) * SRV_RING)) &&
+                      quiet_ok(hipMalloc((void **)&S->d_slab, S->slab_stride * 4 * S->n_blocks)) &&
+                      quiet_ok(hipHostMalloc((void **)&S->ring, sizeof(SrvEntry) * SRV_RING, hipHostMallocDefault)) &&
+                      quiet_ok(hipHostMalloc((void **)&S->exit_word, 256, hipHostMallocDefault)) &&
+                      quiet_ok(hipHostGetDevicePointer(&ring_dev, S->ring, 0)) && quiet_ok(hipHostGetDevicePointer(&exit_dev, S->exit_word, 0));
     if (!good) return S;
     memset(S->ring, 0, sizeof(SrvEntry) * SRV_RING);
     memset(S->exit_word, 0, 256);
@@ -160,10 +150,10 @@ void observe_exit(Server &S) {
 // for the server look again (server_region_wait) and launch it when those are through.
 bool launch_locked(Server &S, const Switches &sw) {
     if (region_calls_in_flight(S.device) > 0) return true;
-    DevGuard dg(S.device);
+    DeviceGuard dg(S.device);
     if (sw.server_trace && !S.d_trace) {
         S.trace_cap = 1u << 20;
-        if (!hip_ok(hipMalloc((void **)&S.d_trace, sizeof(SrvTrace) * S.trace_cap))) S.d_trace = nullptr;
+        if (!quiet_ok(hipMalloc((void **)&S.d_trace, sizeof(SrvTrace) * S.trace_cap))) S.d_trace = nullptr;
     }
     SrvParams P{};
     P.ctl = (SrvCtl *)S.d_block;
@@ -178,7 +168,7 @@ bool launch_locked(Server &S, const Switches &sw) {
     P.stall_ticks = 100u * 1000u * (uint32_t)kServerStallMs;
     P.trace = sw.server_trace ? S.d_trace : nullptr;
     P.trace_cap = S.trace_cap;
-    if (!hip_ok(hipMemsetAsync(S.d_block, 0, S.block_bytes, S.stream)) || !hip_ok(launch_server(P, S.n_blocks, S.stream))) {
+    if (!quiet_ok(hipMemsetAsync(S.d_block, 0, S.block_bytes, S.stream)) || !quiet_ok(launch_server(P, S.n_blocks, S.stream))) {
         S.broken = true;
         S.why_broken = "the region server could not be launched";
         return false;
@@ -198,11 +188,11 @@ int take_slot(Server &S) {
         return slot;
     }
     if (S.n_slots >= kMaxSlots) return -1;
-    DevGuard dg(S.device);
+    DeviceGuard dg(S.device);
     Slot &T = S.slots[S.n_slots];
     void *dp = nullptr;
-    if (hip_ok(hipMalloc((void **)&T.dev, kSlotBytes)) && hip_ok(hipMalloc((void **)&T.sync, kSyncBytes)) &&
-        hip_ok(hipHostMalloc((void **)&T.host, kSlotBytes, hipHostMallocDefault)) && hip_ok(hipHostGetDevicePointer(&dp, T.host, 0)) && dp) {
+    if (quiet_ok(hipMalloc((void **)&T.dev, kSlotBytes)) && quiet_ok(hipMalloc((void **)&T.sync, kSyncBytes)) &&
+        quiet_ok(hipHostMalloc((void **)&T.host, kSlotBytes, hipHostMallocDefault)) && quiet_ok(hipHostGetDevicePointer(&dp, T.host, 0)) && dp) {
         T.host_dev = (char *)dp;
         return S.n_slots++;
     }
@@ -737,7 +727,7 @@ void server_quiesce(int device) {
         S = g_servers[device % kMaxDevices];
     }
     if (!S || !S->ok || S->broken) return;
-    DevGuard dg(device);
+    DeviceGuard dg(device);
     (void)hipStreamSynchronize(S->stream);
     std::lock_guard<SpinLock> lk(S->mu);
     observe_exit(*S);
@@ -751,13 +741,13 @@ uint32_t server_trace_read(int device, phmm::SrvTrace *out, uint32_t cap) {
         S = g_servers[device % kMaxDevices];
     }
     if (!S || !S->ok || !S->d_trace) return 0;
-    DevGuard dg(device);
+    DeviceGuard dg(device);
     (void)hipStreamSynchronize(S->stream);
     uint32_t n = 0;
     const SrvCtl *ctl = (const SrvCtl *)S->d_block;
-    if (!hip_ok(hipMemcpy(&n, &ctl->trace_count, 4, hipMemcpyDeviceToHost))) return 0;
+    if (!quiet_ok(hipMemcpy(&n, &ctl->trace_count, 4, hipMemcpyDeviceToHost))) return 0;
     const uint32_t have = std::min(n, S->trace_cap);
-    if (out && cap && have && !hip_ok(hipMemcpy(out, S->d_trace, sizeof(SrvTrace) * std::min(have, cap), hipMemcpyDeviceToHost))) return 0;
+    if (out && cap && have && !quiet_ok(hipMemcpy(out, S->d_trace, sizeof(SrvTrace) * std::min(have, cap), hipMemcpyDeviceToHost))) return 0;
     return have;
 }
 

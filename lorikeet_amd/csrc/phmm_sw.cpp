@@ -12,31 +12,13 @@
 
 #include "phmm_cigar_internal.hpp"
 #include "phmm_host.hpp"
+#include "phmm_staging.hpp"
 #include "phmm_sw_internal.hpp"
 
 using namespace phmm;
+using namespace phmm_host;
 
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-bool ok(phmm_handle *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    h->err_code = PHMM_ERR_HIP;
-    return false;
-}
 
 // The best-allele step (phmm_best_alleles, and in front of the alignments of phmm_realign_to_best).
 struct BestJob {
@@ -166,22 +148,6 @@ BestParams best_params(const BestJob &b, const BestLayout &L, char *dev, char *o
     p.confidence = (double *)(out + L.conf);
     p.ref_index = d_ref_index;
     return p;
-}
-
-bool grow_staging(phmm_handle *h, size_t total) {
-    phmm_handle::SwWork &W = h->swork;
-    if (W.cap >= total) return true;
-    for (int i = 0; i < 3; ++i) (void)hipStreamSynchronize(h->streams[i]);
-    if (W.dev) (void)hipFree(W.dev);
-    if (W.host) (void)hipHostFree(W.host);
-    W.dev = W.host = W.host_dev = nullptr;
-    W.cap = 0;
-    const size_t cap = std::max<size_t>(total + total / 2, 1 << 20);
-    if (!ok(h, hipMalloc((void **)&W.dev, cap), "hipMalloc(sw staging)") ||
-        !ok(h, hipHostMalloc((void **)&W.host, cap, hipHostMallocDefault), "hipHostMalloc(sw staging)"))
-        return false;
-    W.cap = cap;
-    return true;
 }
 
 }  // namespace
@@ -380,7 +346,7 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     if (!J.ref_bases || !J.alt_bases || (n_cig && !J.cigar && !on_device)) return fail(h, who + ": null array");
     const bool indexed = J.ref_index || J.best;  // references are shared: they all travel with the first piece
 
-    DevGuard dg(h->device);
+    DeviceGuard dg(h->device);
     // ---- geometry (sw_plan above) ------------------------------------------------------------------------------
     phmm_host::SwGeometry G;
     {
@@ -427,6 +393,7 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     for (int c = 0; c < n_chunks; ++c) most = std::max<size_t>(most, cut[c + 1] - cut[c]);
     const size_t slab_bytes = std::min<size_t>(max_workers, (most + gpb - 1) / gpb) * slab_stride * 4;
     phmm_handle::SwWork &W = h->swork;
+    StagingBuffer &SB = W.staging;
     if (G.ext_stride) {  // (giant sequences only)
         const size_t need = std::min<size_t>(max_workers, (most + gpb - 1) / gpb) * G.ext_stride;
         if (W.ext_bytes < need) {
@@ -434,7 +401,7 @@ int sw_run(phmm_handle *h, const SwJob &J) {
             if (W.ext) (void)hipFree(W.ext);
             W.ext = nullptr;
             W.ext_bytes = 0;
-            if (!ok(h, hipMalloc((void **)&W.ext, need), "hipMalloc(sw rows)")) return PHMM_ERR_HIP;
+            if (!hip_ok(h, hipMalloc((void **)&W.ext, need), "hipMalloc(sw rows)")) return PHMM_ERR_HIP;
             W.ext_bytes = need;
         }
     }
@@ -459,7 +426,7 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         if (W.slab) (void)hipFree(W.slab);
         W.slab = nullptr;
         W.slab_bytes = 0;
-        if (!ok(h, hipMalloc((void **)&W.slab, slab_bytes), "hipMalloc(sw backtrack)")) return PHMM_ERR_HIP;
+        if (!hip_ok(h, hipMalloc((void **)&W.slab, slab_bytes), "hipMalloc(sw backtrack)")) return PHMM_ERR_HIP;
         W.slab_bytes = slab_bytes;
     }
     // ---- staging: [status | ref_off | alt_off | cigar_off | ref_index | best-allele inputs, results | ref | alt] in,
@@ -484,22 +451,22 @@ int sw_run(phmm_handle *h, const SwJob &J) {
                  o_extra = o_pout + (PJ ? up256(4ull * pj_out) : 0), o_todo = o_extra + (J.view ? up256(J.view->extra_bytes) : 0),
                  o_patch = o_todo + up256(4ull * n_alignments),  // (the list of the tags-only pass: device memory only)
                  patch_bytes = 4ull * kPatchMax * (3 + max_slot), total = o_patch + (deferred ? up256(patch_bytes) : 0);
-    if (!grow_staging(h, total)) return PHMM_ERR_HIP;
+    if (!SB.grow(h, total, "sw staging")) return PHMM_ERR_HIP;
     // A small call in one piece (a region per call, the reference's pattern): the kernels store the results -- and the
     // status block -- straight into the pinned mirror, so that nothing is copied back (each copy costs the call some
     // 10 us, and the copy engine is what concurrent callers end up queueing for).  What a later kernel reads again (the
     // reference index, the alignments the projection consumes) stays in device memory.
     const size_t result_bytes = (PJ ? o_extra - o_pst : J.view ? 0 : o_pfl - o_nc) + (J.best ? BL.end - BL.best : 0);
     bool zero_copy = one_piece && !h->sw.sw_no_zero_copy && result_bytes <= kZeroCopyResultBytes;
-    if (zero_copy && !W.host_dev) {
+    if (zero_copy && !SB.host_dev) {
         void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, W.host, 0) == hipSuccess && dp)
-            W.host_dev = (char *)dp;
+        if (hipHostGetDevicePointer(&dp, SB.host, 0) == hipSuccess && dp)
+            SB.host_dev = (char *)dp;
         else
             zero_copy = false;
     }
-    char *const out_base = zero_copy ? W.host_dev : W.dev;          // results
-    char *const st_base = zero_copy ? W.host_dev + o_st : W.dev;    // the status block
+    char *const out_base = zero_copy ? SB.host_dev : SB.dev;          // results
+    char *const st_base = zero_copy ? SB.host_dev + o_st : SB.dev;    // the status block
     uint32_t pj_capacity = 0;
     if (PJ) {  // the lanes' builders: see phmm_cigar.cpp
         pj_capacity = 4 * (PJ->sw_capacity + PJ->max_hap_cigar + 2) + 8;
@@ -509,7 +476,7 @@ int sw_run(phmm_handle *h, const SwJob &J) {
             if (W.ws) (void)hipFree(W.ws);
             W.ws = nullptr;
             W.ws_bytes = 0;
-            if (!ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(project workspace)")) return PHMM_ERR_HIP;
+            if (!hip_ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(project workspace)")) return PHMM_ERR_HIP;
             W.ws_bytes = ws_bytes;
         }
     }
@@ -525,24 +492,24 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         h->err_code = keep_code;
     }
     for (int c = 0; c < n_chunks; ++c)  // (each event under its own check: a failure half way must not leave the piece with null events for good)
-        if ((!W.ev_in[c] && !ok(h, hipEventCreateWithFlags(&W.ev_in[c], hipEventDisableTiming), "hipEventCreate")) ||
-            (!W.ev_out[c] && !ok(h, hipEventCreateWithFlags(&W.ev_out[c], hipEventDisableTiming), "hipEventCreate")) ||
-            (!W.ev_k0[c] && !ok(h, hipEventCreate(&W.ev_k0[c]), "hipEventCreate")) ||
-            (!W.ev_k1[c] && !ok(h, hipEventCreate(&W.ev_k1[c]), "hipEventCreate")))
+        if ((!W.ev_in[c] && !hip_ok(h, hipEventCreateWithFlags(&W.ev_in[c], hipEventDisableTiming), "hipEventCreate")) ||
+            (!W.ev_out[c] && !hip_ok(h, hipEventCreateWithFlags(&W.ev_out[c], hipEventDisableTiming), "hipEventCreate")) ||
+            (!W.ev_k0[c] && !hip_ok(h, hipEventCreate(&W.ev_k0[c]), "hipEventCreate")) ||
+            (!W.ev_k1[c] && !hip_ok(h, hipEventCreate(&W.ev_k1[c]), "hipEventCreate")))
             return PHMM_ERR_HIP;
     SwParams p{};
-    p.ref_off = (const uint32_t *)(W.dev + o_ro);
-    p.alt_off = (const uint32_t *)(W.dev + o_ao);
-    p.cigar_off = (const uint64_t *)(W.dev + o_co);
-    p.ref_index = indexed ? (const uint32_t *)(W.dev + o_ri) : nullptr;
-    p.ref_bases = (const uint8_t *)(W.dev + o_rb);
-    p.alt_bases = (const uint8_t *)(W.dev + o_ab);
+    p.ref_off = (const uint32_t *)(SB.dev + o_ro);
+    p.alt_off = (const uint32_t *)(SB.dev + o_ao);
+    p.cigar_off = (const uint64_t *)(SB.dev + o_co);
+    p.ref_index = indexed ? (const uint32_t *)(SB.dev + o_ri) : nullptr;
+    p.ref_bases = (const uint8_t *)(SB.dev + o_rb);
+    p.alt_bases = (const uint8_t *)(SB.dev + o_ab);
     p.w_match = params->match_value;
     p.w_mismatch = params->mismatch_penalty;
     p.w_open = params->gap_open_penalty;
     p.w_extend = params->gap_extend_penalty;
     p.strategy = J.strategy;
-    char *const sw_out = on_device ? W.dev : out_base;  // (alignments that a kernel consumes stay on the device)
+    char *const sw_out = on_device ? SB.dev : out_base;  // (alignments that a kernel consumes stay on the device)
     p.cigar = (uint32_t *)(sw_out + o_cg);
     p.n_cigar = (uint32_t *)(sw_out + o_nc);
     p.alignment_offset = (int32_t *)(sw_out + o_of);
@@ -560,21 +527,21 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     p.ext_stride = G.ext_stride;
     // the offset arrays, the status word, the index and the best-allele inputs travel with the first piece -- and, when
     // the references are shared (reads -> their haplotypes), all the references
-    memset(W.host, 0, 256);
-    if (zero_copy) memset(W.host + o_st, 0, 256);
-    memcpy(W.host + o_ro, ref_off, 4ull * (n_refs + 1));
-    memcpy(W.host + o_ao, alt_off, 4ull * (n_alignments + 1));
-    memcpy(W.host + o_co, cigar_off, 8ull * (n_alignments + 1));
-    if (J.ref_index) memcpy(W.host + o_ri, J.ref_index, 4ull * n_alignments);
+    memset(SB.host, 0, 256);
+    if (zero_copy) memset(SB.host + o_st, 0, 256);
+    memcpy(SB.host + o_ro, ref_off, 4ull * (n_refs + 1));
+    memcpy(SB.host + o_ao, alt_off, 4ull * (n_alignments + 1));
+    memcpy(SB.host + o_co, cigar_off, 8ull * (n_alignments + 1));
+    if (J.ref_index) memcpy(SB.host + o_ri, J.ref_index, 4ull * n_alignments);
     size_t head = J.ref_index ? o_bi : o_ri;
     if (J.best) {
-        stage_best(*J.best, BL, W.host, one_piece);
+        stage_best(*J.best, BL, SB.host, one_piece);
         head = BL.best;
     }
     ProjectParams pp{};
     if (PJ) {
         auto put = [&](size_t at, const void *src, size_t bytes) {
-            if (bytes) memcpy(W.host + at, src, bytes);
+            if (bytes) memcpy(SB.host + at, src, bytes);
         };
         put(p_rrh, PJ->region_ref_hap, 4ull * pj_regions);
         put(p_rs, PJ->region_reference_start, 8ull * pj_regions);
@@ -585,25 +552,25 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         put(p_oc, PJ->orig_cigar, 4ull * pj_oc);
         put(p_oo, PJ->out_cigar_off, 8ull * (n_alignments + 1));
         pp.n_regions = pj_regions;
-        pp.region_read_off = (const uint32_t *)(W.dev + BL.rro);
-        pp.region_hap_off = (const uint32_t *)(W.dev + BL.rho);
+        pp.region_read_off = (const uint32_t *)(SB.dev + BL.rro);
+        pp.region_hap_off = (const uint32_t *)(SB.dev + BL.rho);
         pp.read_off = p.alt_off;
         pp.read_bases = p.alt_bases;
         pp.hap_off = p.ref_off;
         pp.hap_bases = p.ref_bases;
-        pp.region_ref_hap = (const int32_t *)(W.dev + p_rrh);
-        pp.region_reference_start = (const uint64_t *)(W.dev + p_rs);
-        pp.hap_cigar_off = (const uint32_t *)(W.dev + p_hco);
-        pp.hap_cigar = (const uint32_t *)(W.dev + p_hc);
-        pp.hap_start_wrt_ref = (const uint32_t *)(W.dev + p_hs);
+        pp.region_ref_hap = (const int32_t *)(SB.dev + p_rrh);
+        pp.region_reference_start = (const uint64_t *)(SB.dev + p_rs);
+        pp.hap_cigar_off = (const uint32_t *)(SB.dev + p_hco);
+        pp.hap_cigar = (const uint32_t *)(SB.dev + p_hc);
+        pp.hap_start_wrt_ref = (const uint32_t *)(SB.dev + p_hs);
         pp.best_allele = (const int32_t *)(out_base + BL.best);
         pp.sw_cigar_off = p.cigar_off;
         pp.sw_cigar = p.cigar;
         pp.n_sw_cigar = p.n_cigar;
         pp.sw_offset = p.alignment_offset;
-        pp.orig_cigar_off = (const uint32_t *)(W.dev + p_oco);
-        pp.orig_cigar = (const uint32_t *)(W.dev + p_oc);
-        pp.out_cigar_off = (const uint64_t *)(W.dev + p_oo);
+        pp.orig_cigar_off = (const uint32_t *)(SB.dev + p_oco);
+        pp.orig_cigar = (const uint32_t *)(SB.dev + p_oc);
+        pp.out_cigar_off = (const uint64_t *)(SB.dev + p_oo);
         pp.out_cigar = (uint32_t *)(out_base + o_pout);
         pp.n_out_cigar = (uint32_t *)(out_base + o_pno);
         pp.new_pos = (int64_t *)(out_base + o_ppos);
@@ -613,28 +580,28 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         pp.capacity = pj_capacity;
     }
     if (one_piece) {  // the whole input is one contiguous block of the staging buffer
-        memcpy(W.host + o_rb, J.ref_bases, rb);
-        memcpy(W.host + o_ab, J.alt_bases, ab);
+        memcpy(SB.host + o_rb, J.ref_bases, rb);
+        memcpy(SB.host + o_ab, J.alt_bases, ab);
         head = in_bytes;
     }
     bool good;
     if (J.best && !one_piece) {
         // a call in pieces: everything of the head but the likelihood matrix, which is the bulk of it (8 bytes per read
         // and haplotype) and travels with the pieces -- each piece's rows, then the best alleles of its reads
-        good = ok(h, hipMemcpyAsync(W.dev, W.host, BL.lk, hipMemcpyHostToDevice, S_in), "H2D sw") &&
-               (BL.best == BL.keep || ok(h, hipMemcpyAsync(W.dev + BL.keep, W.host + BL.keep, BL.best - BL.keep, hipMemcpyHostToDevice, S_in), "H2D sw"));
+        good = hip_ok(h, hipMemcpyAsync(SB.dev, SB.host, BL.lk, hipMemcpyHostToDevice, S_in), "H2D sw") &&
+               (BL.best == BL.keep || hip_ok(h, hipMemcpyAsync(SB.dev + BL.keep, SB.host + BL.keep, BL.best - BL.keep, hipMemcpyHostToDevice, S_in), "H2D sw"));
     } else {
         // (a small call's inputs are fetched by a kernel: no copy engine, no cross-engine dependency for the launches behind it)
-        good = zero_copy && head <= kStageInBytes ? ok(h, launch_stage_in(W.host_dev, W.dev, head, S_in), "phmm_stage_in_kernel")
-                                                  : ok(h, hipMemcpyAsync(W.dev, W.host, head, hipMemcpyHostToDevice, S_in), "H2D sw");
+        good = zero_copy && head <= kStageInBytes ? hip_ok(h, launch_stage_in(SB.host_dev, SB.dev, head, S_in), "phmm_stage_in_kernel")
+                                                  : hip_ok(h, hipMemcpyAsync(SB.dev, SB.host, head, hipMemcpyHostToDevice, S_in), "H2D sw");
     }
     if (good && J.best && one_piece)  // the reads' best alleles become the index of their references, on the device
-        good = ok(h, launch_best_alleles(best_params(*J.best, BL, W.dev, out_base, (uint32_t *)(W.dev + o_ri)), S_in), "phmm_best_alleles_kernel");
+        good = hip_ok(h, launch_best_alleles(best_params(*J.best, BL, SB.dev, out_base, (uint32_t *)(SB.dev + o_ri)), S_in), "phmm_best_alleles_kernel");
     if (good && PJ && !one_piece)  // the projection's inputs follow the head
-        good = ok(h, hipMemcpyAsync(W.dev + o_pi, W.host + o_pi, p_end - o_pi, hipMemcpyHostToDevice, S_in), "H2D project");
+        good = hip_ok(h, hipMemcpyAsync(SB.dev + o_pi, SB.host + o_pi, p_end - o_pi, hipMemcpyHostToDevice, S_in), "H2D project");
     if (good && indexed && !one_piece) {
-        memcpy(W.host + o_rb, J.ref_bases, rb);
-        good = ok(h, hipMemcpyAsync(W.dev + o_rb, W.host + o_rb, rb, hipMemcpyHostToDevice, S_in), "H2D sw");
+        memcpy(SB.host + o_rb, J.ref_bases, rb);
+        good = hip_ok(h, hipMemcpyAsync(SB.dev + o_rb, SB.host + o_rb, rb, hipMemcpyHostToDevice, S_in), "H2D sw");
     }
     h->stat_staged_bytes += rb + ab;
     for (int c = 0; c < n_chunks && good; ++c) {
@@ -651,23 +618,23 @@ int sw_run(phmm_handle *h, const SwJob &J) {
             uint32_t nh0 = 0, nh1 = 0;
             const uint64_t lo = row_of(a0, &nh0), hi = row_of(a1 - 1, &nh1) + nh1;
             if (hi > lo) {
-                memcpy(W.host + BL.lk + 8ull * lo, B.likelihoods + lo, 8ull * (hi - lo));
-                good = ok(h, hipMemcpyAsync(W.dev + BL.lk + 8ull * lo, W.host + BL.lk + 8ull * lo, 8ull * (hi - lo), hipMemcpyHostToDevice, S_in), "H2D sw");
+                memcpy(SB.host + BL.lk + 8ull * lo, B.likelihoods + lo, 8ull * (hi - lo));
+                good = hip_ok(h, hipMemcpyAsync(SB.dev + BL.lk + 8ull * lo, SB.host + BL.lk + 8ull * lo, 8ull * (hi - lo), hipMemcpyHostToDevice, S_in), "H2D sw");
             }
-            BestParams bp = best_params(B, BL, W.dev, out_base, (uint32_t *)(W.dev + o_ri));
+            BestParams bp = best_params(B, BL, SB.dev, out_base, (uint32_t *)(SB.dev + o_ri));
             bp.r_begin = a0;
             bp.n_reads = a1;
-            good = good && ok(h, launch_best_alleles(bp, S_in), "phmm_best_alleles_kernel");
+            good = good && hip_ok(h, launch_best_alleles(bp, S_in), "phmm_best_alleles_kernel");
         }
         if (!one_piece) {
             if (!indexed) {  // one reference per alignment: they travel piece by piece like the alternates
                 const size_t r0 = ref_off[a0], r1 = ref_off[a1];
-                memcpy(W.host + o_rb + r0, J.ref_bases + r0, r1 - r0);
-                good = r1 == r0 || ok(h, hipMemcpyAsync(W.dev + o_rb + r0, W.host + o_rb + r0, r1 - r0, hipMemcpyHostToDevice, S_in), "H2D sw");
+                memcpy(SB.host + o_rb + r0, J.ref_bases + r0, r1 - r0);
+                good = r1 == r0 || hip_ok(h, hipMemcpyAsync(SB.dev + o_rb + r0, SB.host + o_rb + r0, r1 - r0, hipMemcpyHostToDevice, S_in), "H2D sw");
             }
-            memcpy(W.host + o_ab + q0, J.alt_bases + q0, q1 - q0);
-            good = good && (q1 == q0 || ok(h, hipMemcpyAsync(W.dev + o_ab + q0, W.host + o_ab + q0, q1 - q0, hipMemcpyHostToDevice, S_in), "H2D sw")) &&
-                   ok(h, hipEventRecord(W.ev_in[c], S_in), "hipEventRecord") && ok(h, hipStreamWaitEvent(S, W.ev_in[c], 0), "hipStreamWaitEvent");
+            memcpy(SB.host + o_ab + q0, J.alt_bases + q0, q1 - q0);
+            good = good && (q1 == q0 || hip_ok(h, hipMemcpyAsync(SB.dev + o_ab + q0, SB.host + o_ab + q0, q1 - q0, hipMemcpyHostToDevice, S_in), "H2D sw")) &&
+                   hip_ok(h, hipEventRecord(W.ev_in[c], S_in), "hipEventRecord") && hip_ok(h, hipStreamWaitEvent(S, W.ev_in[c], 0), "hipStreamWaitEvent");
         }
         if (!good || a1 == a0) continue;
         p.a_begin = a0;
@@ -676,12 +643,12 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         (void)hipEventRecord(W.ev_k0[c], S);
         if (lite) {  // tags only, then the full instance over what met a gap (the counters are zeroed with the head of the input)
             SwParams p1 = p, p2 = p;
-            p1.todo_out = (uint32_t *)(W.dev + o_todo) + (deferred || deferred_project ? 0 : a0);
-            p1.todo_out_count = (uint32_t *)(W.dev + 192) + (deferred || deferred_project ? 0 : c);
+            p1.todo_out = (uint32_t *)(SB.dev + o_todo) + (deferred || deferred_project ? 0 : a0);
+            p1.todo_out_count = (uint32_t *)(SB.dev + 192) + (deferred || deferred_project ? 0 : c);
             p2.todo = p1.todo_out;
             p2.todo_count = p1.todo_out_count;
-            p2.feedback = zero_copy ? (uint32_t *)(W.host_dev + o_st + 192) + c : nullptr;  // (otherwise the counters come back with the status block)
-            good = ok(h, launch_sw(L, K, transposed, SW_LITE, p1, (uint32_t)workers, lds, S), "phmm_sw_align_kernel (tags)");
+            p2.feedback = zero_copy ? (uint32_t *)(SB.host_dev + o_st + 192) + c : nullptr;  // (otherwise the counters come back with the status block)
+            good = hip_ok(h, launch_sw(L, K, transposed, SW_LITE, p1, (uint32_t)workers, lds, S), "phmm_sw_align_kernel (tags)");
             if (deferred || deferred_project) {  // (the second pass follows the last piece)
                 (void)hipEventRecord(W.ev_k1[c], S);
                 continue;
@@ -700,27 +667,27 @@ int sw_run(phmm_handle *h, const SwJob &J) {
                 ps.todo_max = kShortList;
                 p2.todo_min = kShortList + 1;
                 const size_t fit = W.slab_bytes / (GS.slab_stride * 4);
-                good = ok(h, launch_sw(GS.L, GS.K, GS.transposed, GS.variant, ps, (uint32_t)std::min<size_t>({(size_t)kShortList, fit, GS.max_workers}), GS.lds, S),
+                good = hip_ok(h, launch_sw(GS.L, GS.K, GS.transposed, GS.variant, ps, (uint32_t)std::min<size_t>({(size_t)kShortList, fit, GS.max_workers}), GS.lds, S),
                           "phmm_sw_align_kernel (short list)");
             }
-            good = good && ok(h, launch_sw(L, K, transposed, G.variant, p2, (uint32_t)workers, lds, S), "phmm_sw_align_kernel");
+            good = good && hip_ok(h, launch_sw(L, K, transposed, G.variant, p2, (uint32_t)workers, lds, S), "phmm_sw_align_kernel");
         } else {
-            good = ok(h, launch_sw(L, K, transposed, G.variant, p, (uint32_t)workers, lds, S), "phmm_sw_align_kernel");
+            good = hip_ok(h, launch_sw(L, K, transposed, G.variant, p, (uint32_t)workers, lds, S), "phmm_sw_align_kernel");
         }
         if (good && PJ) {  // ... and the piece's alignments projected onto the reference, where they lie
             pp.r_begin = a0;
             pp.n_reads = a1;
-            good = ok(h, launch_project(pp, S), "phmm_project_kernel");
+            good = hip_ok(h, launch_project(pp, S), "phmm_project_kernel");
         }
         (void)hipEventRecord(W.ev_k1[c], S);
     }
     if ((deferred || deferred_project) && good) {
-        if (!W.ev_second && !ok(h, hipEventCreate(&W.ev_second), "hipEventCreate")) return PHMM_ERR_HIP;
+        if (!W.ev_second && !hip_ok(h, hipEventCreate(&W.ev_second), "hipEventCreate")) return PHMM_ERR_HIP;
         SwParams p2 = p;
         p2.a_begin = 0;
         p2.n_alignments = n_alignments;
-        p2.todo = (const uint32_t *)(W.dev + o_todo);
-        p2.todo_count = (const uint32_t *)(W.dev + 192);
+        p2.todo = (const uint32_t *)(SB.dev + o_todo);
+        p2.todo_count = (const uint32_t *)(SB.dev + 192);
         if (have_short) {
             SwParams ps = p2;
             ps.lds_ref_bytes = (uint32_t)GS.lds_ref;
@@ -731,21 +698,21 @@ int sw_run(phmm_handle *h, const SwJob &J) {
             ps.todo_max = kShortList;
             p2.todo_min = kShortList + 1;
             const size_t fit = W.slab_bytes / (GS.slab_stride * 4);
-            good = ok(h, launch_sw(GS.L, GS.K, GS.transposed, GS.variant, ps, (uint32_t)std::min<size_t>({(size_t)kShortList, fit, GS.max_workers}), GS.lds, S),
+            good = hip_ok(h, launch_sw(GS.L, GS.K, GS.transposed, GS.variant, ps, (uint32_t)std::min<size_t>({(size_t)kShortList, fit, GS.max_workers}), GS.lds, S),
                       "phmm_sw_align_kernel (short list)");
         }
         const size_t all_workers = std::min<size_t>({max_workers, ((size_t)n_alignments + gpb - 1) / gpb, W.slab_bytes / (slab_stride * 4)});
-        good = good && ok(h, launch_sw(L, K, transposed, G.variant, p2, (uint32_t)all_workers, lds, S), "phmm_sw_align_kernel");
+        good = good && hip_ok(h, launch_sw(L, K, transposed, G.variant, p2, (uint32_t)all_workers, lds, S), "phmm_sw_align_kernel");
         if (deferred)
-            good = good && ok(h, launch_sw_gather(p2.todo, p2.todo_count, p.n_cigar, p.alignment_offset, p.cigar, p.cigar_off, (uint32_t)max_slot,
-                                                  kPatchMax, (uint32_t *)(W.dev + o_patch), S), "phmm_sw_gather_kernel");
+            good = good && hip_ok(h, launch_sw_gather(p2.todo, p2.todo_count, p.n_cigar, p.alignment_offset, p.cigar, p.cigar_off, (uint32_t)max_slot,
+                                                  kPatchMax, (uint32_t *)(SB.dev + o_patch), S), "phmm_sw_gather_kernel");
         for (int c = 0; c < n_chunks && good && deferred_project; ++c) {  // (piece by piece: the workspace is a piece's)
             if (cut[c + 1] == cut[c]) continue;
             pp.r_begin = cut[c];
             pp.n_reads = cut[c + 1];
-            good = ok(h, launch_project(pp, S), "phmm_project_kernel");
+            good = hip_ok(h, launch_project(pp, S), "phmm_project_kernel");
         }
-        good = good && ok(h, hipEventRecord(W.ev_second, S), "hipEventRecord");
+        good = good && hip_ok(h, hipEventRecord(W.ev_second, S), "hipEventRecord");
     }
     // (while the device works) what the kernels store per alignment: (rows + L - 1) steps x L lanes x flag words per strip
     W.last_backtrack_bytes = 0;
@@ -765,20 +732,20 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     hipStream_t S_out = one_piece ? S : h->streams[2];
     auto unpack = [&](int c) {
         const uint32_t a0 = cut[c], a1 = cut[c + 1];
-        if (!one_piece && !ok(h, hipEventSynchronize(W.ev_out[c]), "sync(sw results)")) return false;  // (one piece: the stream has been waited for)
+        if (!one_piece && !hip_ok(h, hipEventSynchronize(W.ev_out[c]), "sync(sw results)")) return false;  // (one piece: the stream has been waited for)
         if (J.view && !PJ) return true;
         if (PJ) {
-            memcpy(PJ->status + a0, W.host + o_pst + 4ull * a0, 4ull * (a1 - a0));
-            memcpy(PJ->n_out_cigar + a0, W.host + o_pno + 4ull * a0, 4ull * (a1 - a0));
-            memcpy(PJ->new_pos + a0, W.host + o_ppos + 8ull * a0, 8ull * (a1 - a0));
+            memcpy(PJ->status + a0, SB.host + o_pst + 4ull * a0, 4ull * (a1 - a0));
+            memcpy(PJ->n_out_cigar + a0, SB.host + o_pno + 4ull * a0, 4ull * (a1 - a0));
+            memcpy(PJ->new_pos + a0, SB.host + o_ppos + 8ull * a0, 8ull * (a1 - a0));
             const uint64_t q0 = PJ->out_cigar_off[a0], q1 = PJ->out_cigar_off[a1];
-            if (q1 > q0) memcpy(PJ->out_cigar + q0, W.host + o_pout + 4ull * q0, 4ull * (q1 - q0));
+            if (q1 > q0) memcpy(PJ->out_cigar + q0, SB.host + o_pout + 4ull * q0, 4ull * (q1 - q0));
             return true;
         }
-        memcpy(J.n_cigar + a0, W.host + o_nc + 4ull * a0, 4ull * (a1 - a0));
-        memcpy(J.alignment_offset + a0, W.host + o_of + 4ull * a0, 4ull * (a1 - a0));
+        memcpy(J.n_cigar + a0, SB.host + o_nc + 4ull * a0, 4ull * (a1 - a0));
+        memcpy(J.alignment_offset + a0, SB.host + o_of + 4ull * a0, 4ull * (a1 - a0));
         if (cigar_off[a1] > cigar_off[a0])
-            memcpy(J.cigar + cigar_off[a0], W.host + o_cg + 4ull * cigar_off[a0], 4ull * (cigar_off[a1] - cigar_off[a0]));
+            memcpy(J.cigar + cigar_off[a0], SB.host + o_cg + 4ull * cigar_off[a0], 4ull * (cigar_off[a1] - cigar_off[a0]));
         return true;
     };
     int prev = -1, last_piece = 0;
@@ -789,43 +756,43 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         const uint32_t a0 = cut[c], a1 = cut[c + 1];
         if (a1 == a0) continue;
         const uint64_t g0 = cigar_off[a0], g1 = cigar_off[a1];
-        good = one_piece || ok(h, hipEventSynchronize(deferred_project ? W.ev_second : W.ev_k1[c]), "sync(sw kernel)");
+        good = one_piece || hip_ok(h, hipEventSynchronize(deferred_project ? W.ev_second : W.ev_k1[c]), "sync(sw kernel)");
         if (zero_copy) {
             // nothing to fetch
         } else if (one_piece) {  // the piece is the call: its results are one contiguous block of the staging buffer
             const size_t from = PJ ? o_pst : o_nc, to = PJ ? o_extra : o_pfl;
-            good = good && (J.view && !PJ ? true : ok(h, hipMemcpyAsync(W.host + from, W.dev + from, to - from, hipMemcpyDeviceToHost, S_out), "D2H sw"));
+            good = good && (J.view && !PJ ? true : hip_ok(h, hipMemcpyAsync(SB.host + from, SB.dev + from, to - from, hipMemcpyDeviceToHost, S_out), "D2H sw"));
         } else if (PJ) {
             const uint64_t q0 = PJ->out_cigar_off[a0], q1 = PJ->out_cigar_off[a1];
             good = good &&
-                   ok(h, hipMemcpyAsync(W.host + o_pst + 4ull * a0, W.dev + o_pst + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
-                   ok(h, hipMemcpyAsync(W.host + o_pno + 4ull * a0, W.dev + o_pno + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
-                   ok(h, hipMemcpyAsync(W.host + o_ppos + 8ull * a0, W.dev + o_ppos + 8ull * a0, 8ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
-                   (q1 == q0 || ok(h, hipMemcpyAsync(W.host + o_pout + 4ull * q0, W.dev + o_pout + 4ull * q0, 4ull * (q1 - q0), hipMemcpyDeviceToHost, S_out), "D2H project"));
+                   hip_ok(h, hipMemcpyAsync(SB.host + o_pst + 4ull * a0, SB.dev + o_pst + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
+                   hip_ok(h, hipMemcpyAsync(SB.host + o_pno + 4ull * a0, SB.dev + o_pno + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
+                   hip_ok(h, hipMemcpyAsync(SB.host + o_ppos + 8ull * a0, SB.dev + o_ppos + 8ull * a0, 8ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H project") &&
+                   (q1 == q0 || hip_ok(h, hipMemcpyAsync(SB.host + o_pout + 4ull * q0, SB.dev + o_pout + 4ull * q0, 4ull * (q1 - q0), hipMemcpyDeviceToHost, S_out), "D2H project"));
         } else if (!J.view) {
             good = good &&
-                   ok(h, hipMemcpyAsync(W.host + o_nc + 4ull * a0, W.dev + o_nc + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H sw") &&
-                   ok(h, hipMemcpyAsync(W.host + o_of + 4ull * a0, W.dev + o_of + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H sw") &&
-                   (g1 == g0 || ok(h, hipMemcpyAsync(W.host + o_cg + 4ull * g0, W.dev + o_cg + 4ull * g0, 4ull * (g1 - g0), hipMemcpyDeviceToHost, S_out), "D2H sw"));
+                   hip_ok(h, hipMemcpyAsync(SB.host + o_nc + 4ull * a0, SB.dev + o_nc + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H sw") &&
+                   hip_ok(h, hipMemcpyAsync(SB.host + o_of + 4ull * a0, SB.dev + o_of + 4ull * a0, 4ull * (a1 - a0), hipMemcpyDeviceToHost, S_out), "D2H sw") &&
+                   (g1 == g0 || hip_ok(h, hipMemcpyAsync(SB.host + o_cg + 4ull * g0, SB.dev + o_cg + 4ull * g0, 4ull * (g1 - g0), hipMemcpyDeviceToHost, S_out), "D2H sw"));
         }
-        good = good && (one_piece || ok(h, hipEventRecord(W.ev_out[c], S_out), "hipEventRecord"));
+        good = good && (one_piece || hip_ok(h, hipEventRecord(W.ev_out[c], S_out), "hipEventRecord"));
         if (good && J.best && !best_fetched && !zero_copy && c == last_piece) {  // (final once the last piece's kernel has been seen to end)
-            good = ok(h, hipMemcpyAsync(W.host + BL.best, W.dev + BL.best, BL.end - BL.best, hipMemcpyDeviceToHost, S_out), "D2H best alleles");
+            good = hip_ok(h, hipMemcpyAsync(SB.host + BL.best, SB.dev + BL.best, BL.end - BL.best, hipMemcpyDeviceToHost, S_out), "D2H best alleles");
             best_fetched = true;
         }
         if (good && prev >= 0) good = unpack(prev);
         prev = c;
     }
     if (deferred && good)  // the status block and the gathered alignments are final once the second pass is through
-        good = ok(h, hipEventSynchronize(W.ev_second), "sync(sw second pass)") &&
-               ok(h, hipMemcpyAsync(W.host + o_patch, W.dev + o_patch, patch_bytes, hipMemcpyDeviceToHost, S_out), "D2H sw");
-    good = good && (zero_copy || ok(h, hipMemcpyAsync(W.host + o_st, W.dev, 256, hipMemcpyDeviceToHost, S_out), "D2H sw"));
+        good = hip_ok(h, hipEventSynchronize(W.ev_second), "sync(sw second pass)") &&
+               hip_ok(h, hipMemcpyAsync(SB.host + o_patch, SB.dev + o_patch, patch_bytes, hipMemcpyDeviceToHost, S_out), "D2H sw");
+    good = good && (zero_copy || hip_ok(h, hipMemcpyAsync(SB.host + o_st, SB.dev, 256, hipMemcpyDeviceToHost, S_out), "D2H sw"));
     if (one_piece) {
-        good = good && ok(h, hipStreamSynchronize(S_out), "sync(sw)");
+        good = good && hip_ok(h, hipStreamSynchronize(S_out), "sync(sw)");
         if (good && prev >= 0) good = unpack(prev);
     } else {
         if (good && prev >= 0) good = unpack(prev);
-        good = good && ok(h, hipStreamSynchronize(S_out), "sync(sw)");
+        good = good && hip_ok(h, hipStreamSynchronize(S_out), "sync(sw)");
     }
     if (!good) {
         (void)hipStreamSynchronize(S_in);
@@ -834,9 +801,9 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         return PHMM_ERR_HIP;
     }
     if (deferred) {  // what the second pass redid, over what the pieces brought
-        const uint32_t again = *(const uint32_t *)(W.host + o_st + 192);
+        const uint32_t again = *(const uint32_t *)(SB.host + o_st + 192);
         if (again <= kPatchMax) {
-            const uint32_t *e = (const uint32_t *)(W.host + o_patch);
+            const uint32_t *e = (const uint32_t *)(SB.host + o_patch);
             for (uint32_t t = 0; t < again; ++t, e += 3 + max_slot) {
                 const uint32_t a = e[0];
                 J.n_cigar[a] = e[1];
@@ -845,16 +812,16 @@ int sw_run(phmm_handle *h, const SwJob &J) {
                 if (slot) memcpy(J.cigar + cigar_off[a], e + 3, 4ull * std::min<uint64_t>(slot, e[1]));
             }
         } else {  // (a call full of gaps: everything once more; the handle then stops taking the first pass)
-            if (!ok(h, hipMemcpy(W.host + o_nc, W.dev + o_nc, o_pfl - o_nc, hipMemcpyDeviceToHost), "D2H sw")) return PHMM_ERR_HIP;
-            memcpy(J.n_cigar, W.host + o_nc, 4ull * n_alignments);
-            memcpy(J.alignment_offset, W.host + o_of, 4ull * n_alignments);
-            if (n_cig) memcpy(J.cigar, W.host + o_cg, 4ull * n_cig);
+            if (!hip_ok(h, hipMemcpy(SB.host + o_nc, SB.dev + o_nc, o_pfl - o_nc, hipMemcpyDeviceToHost), "D2H sw")) return PHMM_ERR_HIP;
+            memcpy(J.n_cigar, SB.host + o_nc, 4ull * n_alignments);
+            memcpy(J.alignment_offset, SB.host + o_of, 4ull * n_alignments);
+            if (n_cig) memcpy(J.cigar, SB.host + o_cg, 4ull * n_cig);
         }
     }
     if (J.best) {
-        memcpy(J.best->best_allele, W.host + BL.best, 4ull * J.best->n_reads);
-        memcpy(J.best->likelihood, W.host + BL.olk, 8ull * J.best->n_reads);
-        memcpy(J.best->confidence, W.host + BL.conf, 8ull * J.best->n_reads);
+        memcpy(J.best->best_allele, SB.host + BL.best, 4ull * J.best->n_reads);
+        memcpy(J.best->likelihood, SB.host + BL.olk, 8ull * J.best->n_reads);
+        memcpy(J.best->confidence, SB.host + BL.conf, 8ull * J.best->n_reads);
     }
     W.last_kernel_us = 0;
     for (int c = 0; c < n_chunks; ++c) {
@@ -867,11 +834,11 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     }
     if (lite) {
         uint64_t again = 0;
-        for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks); ++c) again += ((const uint32_t *)(W.host + o_st + 192))[c];
+        for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks); ++c) again += ((const uint32_t *)(SB.host + o_st + 192))[c];
         W.last_second_pass = again;
         // (a short list goes to the small-call instance, a longer one to the batch's own; per piece, or once behind the last piece)
         uint64_t first_list = 0;
-        for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks) && !first_list; ++c) first_list = ((const uint32_t *)(W.host + o_st + 192))[c];
+        for (int c = 0; c < (deferred || deferred_project ? 1 : n_chunks) && !first_list; ++c) first_list = ((const uint32_t *)(SB.host + o_st + 192))[c];
         if (again)
             W.last_instance_second = have_short && first_list <= kShortList
                                          ? phmm_host::sw_pack_instance(GS.L, GS.K, GS.transposed, GS.variant, GS.strips)
@@ -880,19 +847,19 @@ int sw_run(phmm_handle *h, const SwJob &J) {
     } else {
         W.last_second_pass = 0;
     }
-    const uint32_t *st = (const uint32_t *)(W.host + o_st + 64);  // [0], [1] conditions; [2], [3]: shader clocks / 100 MHz ticks of the last kernel's block 0
+    const uint32_t *st = (const uint32_t *)(SB.host + o_st + 64);  // [0], [1] conditions; [2], [3]: shader clocks / 100 MHz ticks of the last kernel's block 0
     W.last_clock_mhz = st[3] ? (uint64_t)((double)st[2] * 100.0 / (double)st[3]) : 0;
     if (st[SW_STATUS_EMPTY]) return fail(h, who + empty_msg);  // (an alignment the device met had an empty sequence)
     if (st[SW_STATUS_CAPACITY]) {
         if (on_device) {  // an alignment outgrew the library's own slots: tell the caller how large the largest is (it runs again)
             std::vector<uint32_t> n_cig_host(n_alignments);
-            if (!ok(h, hipMemcpy(n_cig_host.data(), W.dev + o_nc, 4ull * n_alignments, hipMemcpyDeviceToHost), "D2H sw")) return PHMM_ERR_HIP;
+            if (!hip_ok(h, hipMemcpy(n_cig_host.data(), SB.dev + o_nc, 4ull * n_alignments, hipMemcpyDeviceToHost), "D2H sw")) return PHMM_ERR_HIP;
             if (J.sw_capacity_needed) *J.sw_capacity_needed = *std::max_element(n_cig_host.begin(), n_cig_host.end());
         }
         h->err = who + ": a CIGAR needs more elements than its slot holds (n_cigar has the sizes)";
         return h->err_code = PHMM_ERR_CIGAR_CAPACITY;
     }
-    if (PJ && (*(const uint32_t *)(W.host + o_st + 128) & 1u)) {
+    if (PJ && (*(const uint32_t *)(SB.host + o_st + 128) & 1u)) {
         h->err = who + ": a CIGAR needs more elements than its slot holds (n_out_cigar has the sizes)";
         return h->err_code = PHMM_ERR_CIGAR_CAPACITY;
     }
@@ -905,8 +872,8 @@ int sw_run(phmm_handle *h, const SwJob &J) {
         J.view->cigar = p.cigar;
         J.view->n_cigar = p.n_cigar;
         J.view->alignment_offset = p.alignment_offset;
-        J.view->extra_dev = W.dev + o_extra;
-        J.view->extra_host = W.host + o_extra;
+        J.view->extra_dev = SB.dev + o_extra;
+        J.view->extra_host = SB.host + o_extra;
     }
     return PHMM_OK;
 }
@@ -998,20 +965,20 @@ extern "C" int phmm_best_alleles(phmm_handle *h, uint32_t n_regions, const uint3
         }
         const int st = check_best(h, "phmm_best_alleles", B);
         if (st != PHMM_OK || !n_regions || !B.n_reads) return st;
-        DevGuard dg(h->device);
+        DeviceGuard dg(h->device);
         const BestLayout BL(&B, 0);
-        if (!grow_staging(h, BL.end)) return PHMM_ERR_HIP;
-        phmm_handle::SwWork &W = h->swork;
+        StagingBuffer &SB = h->swork.staging;
+        if (!SB.grow(h, BL.end, "sw staging")) return PHMM_ERR_HIP;
         hipStream_t S = h->streams[0];
-        stage_best(B, BL, W.host);
-        if (!ok(h, hipMemcpyAsync(W.dev, W.host, BL.best, hipMemcpyHostToDevice, S), "H2D best alleles") ||
-            !ok(h, launch_best_alleles(best_params(B, BL, W.dev, W.dev, nullptr), S), "phmm_best_alleles_kernel") ||
-            !ok(h, hipMemcpyAsync(W.host + BL.best, W.dev + BL.best, BL.end - BL.best, hipMemcpyDeviceToHost, S), "D2H best alleles") ||
-            !ok(h, hipStreamSynchronize(S), "sync(best alleles)"))
+        stage_best(B, BL, SB.host);
+        if (!hip_ok(h, hipMemcpyAsync(SB.dev, SB.host, BL.best, hipMemcpyHostToDevice, S), "H2D best alleles") ||
+            !hip_ok(h, launch_best_alleles(best_params(B, BL, SB.dev, SB.dev, nullptr), S), "phmm_best_alleles_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(SB.host + BL.best, SB.dev + BL.best, BL.end - BL.best, hipMemcpyDeviceToHost, S), "D2H best alleles") ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(best alleles)"))
             return PHMM_ERR_HIP;
-        memcpy(best_allele, W.host + BL.best, 4ull * B.n_reads);
-        memcpy(likelihood, W.host + BL.olk, 8ull * B.n_reads);
-        memcpy(confidence, W.host + BL.conf, 8ull * B.n_reads);
+        memcpy(best_allele, SB.host + BL.best, 4ull * B.n_reads);
+        memcpy(likelihood, SB.host + BL.olk, 8ull * B.n_reads);
+        memcpy(confidence, SB.host + BL.conf, 8ull * B.n_reads);
         return PHMM_OK;
     });
 }
@@ -1199,7 +1166,7 @@ extern "C" int phmm_calculate_cigar(phmm_handle *h, uint32_t n, const uint32_t *
             st = sw_run(h, J);
         }
         if (st != PHMM_OK) return st;
-        DevGuard dg(h->device);
+        DeviceGuard dg(h->device);
         phmm_handle::SwWork &W = h->swork;
         hipStream_t S = h->streams[0];
         // three arrays per lane: the trimmed cigar (+ one element), left_align_indels' right-to-left list (four per element + 2), its result
@@ -1210,7 +1177,7 @@ extern "C" int phmm_calculate_cigar(phmm_handle *h, uint32_t n, const uint32_t *
             if (W.ws) (void)hipFree(W.ws);
             W.ws = nullptr;
             W.ws_bytes = 0;
-            if (!ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(cigar workspace)")) return PHMM_ERR_HIP;
+            if (!hip_ok(h, hipMalloc((void **)&W.ws, ws_bytes), "hipMalloc(cigar workspace)")) return PHMM_ERR_HIP;
             W.ws_bytes = ws_bytes;
         }
         memset(V.extra_host + x_fl, 0, 256);
@@ -1232,12 +1199,12 @@ extern "C" int phmm_calculate_cigar(phmm_handle *h, uint32_t n, const uint32_t *
         c.flags = (uint32_t *)(V.extra_dev + x_fl);
         c.workspace = W.ws;
         c.capacity = capacity;
-        if (!ok(h, hipMemcpyAsync(V.extra_dev + x_fl, V.extra_host + x_fl, 256, hipMemcpyHostToDevice, S), "H2D cigar") ||
-            !ok(h, hipMemcpyAsync(V.extra_dev + x_oo, V.extra_host + x_oo, 8ull * (n + 1), hipMemcpyHostToDevice, S), "H2D cigar") ||
-            !ok(h, launch_calculate_cigar(c, S), "phmm_calculate_cigar_kernel") ||
-            !ok(h, hipMemcpyAsync(V.extra_host, V.extra_dev, x_oo, hipMemcpyDeviceToHost, S), "D2H cigar") ||
-            (n_out && !ok(h, hipMemcpyAsync(V.extra_host + x_out, V.extra_dev + x_out, 4ull * n_out, hipMemcpyDeviceToHost, S), "D2H cigar")) ||
-            !ok(h, hipStreamSynchronize(S), "sync(cigar)"))
+        if (!hip_ok(h, hipMemcpyAsync(V.extra_dev + x_fl, V.extra_host + x_fl, 256, hipMemcpyHostToDevice, S), "H2D cigar") ||
+            !hip_ok(h, hipMemcpyAsync(V.extra_dev + x_oo, V.extra_host + x_oo, 8ull * (n + 1), hipMemcpyHostToDevice, S), "H2D cigar") ||
+            !hip_ok(h, launch_calculate_cigar(c, S), "phmm_calculate_cigar_kernel") ||
+            !hip_ok(h, hipMemcpyAsync(V.extra_host, V.extra_dev, x_oo, hipMemcpyDeviceToHost, S), "D2H cigar") ||
+            (n_out && !hip_ok(h, hipMemcpyAsync(V.extra_host + x_out, V.extra_dev + x_out, 4ull * n_out, hipMemcpyDeviceToHost, S), "D2H cigar")) ||
+            !hip_ok(h, hipStreamSynchronize(S), "sync(cigar)"))
             return PHMM_ERR_HIP;
         memcpy(status, V.extra_host + x_st, 4ull * n);
         memcpy(n_cigar, V.extra_host + x_no, 4ull * n);
