@@ -77,6 +77,7 @@ extern "C" {
 #define PHMM_ERR_NO_MEMORY 6        /* a host allocation failed (std::bad_alloc never crosses the ABI)    */
 #define PHMM_ERR_INTERNAL 7         /* any other C++ exception inside the library; see phmm_last_error    */
 #define PHMM_ERR_CIGAR_CAPACITY 8   /* phmm_sw_align: a CIGAR did not fit its slot; n_cigar has the sizes */
+#define PHMM_ERR_EVENT_CAPACITY 9   /* phmm_discover_events: an output array is too small; required has the sizes */
 
 typedef struct phmm_handle phmm_handle;
 typedef struct phmm_batch phmm_batch;
@@ -784,6 +785,105 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
                          const uint8_t *sample_called, const double *log10_p_error, const uint32_t *n_filtered, int32_t *ad,
                          int32_t *dp, double *af, uint32_t *ac, uint8_t *mq, uint8_t *bq, int32_t *info_dp, int32_t *qd_depth,
                          double *qd, uint32_t *flags);
+
+/*
+ * Event discovery: the head of the reference's assign_genotype_likelihoods (src/haplotype/haplotype_caller_genotyping_engine.rs:
+ * 125-229), for many regions in ONE call -- what lies between phmm_calculate_cigar and phmm_genotype_likelihoods.  Integer and
+ * byte work: every output EQUALS the reference's.  Per region:
+ *   1. event maps     EventMap::process_cigar_for_initial_events, add_vc, make_block (src/haplotype/event_map.rs:86-344) per
+ *                     haplotype: insertions skipped as first / last element, at ref_pos == 0 or over a base that is not regular
+ *                     (BaseUtils::is_regular_base is "ACGTacgt": N is not, lower case is); deletions skipped at ref_pos == 0 or over
+ *                     such a base; mismatches of an M / = / X element grouped by max_mnp_distance; S advances the haplotype only;
+ *                     events of one start merged into a block (SNP + insertion, SNP + deletion, insertion + deletion, SNP +
+ *                     insertion + deletion).  As written, a block keeps the type of the alleles its FIRST event had (make_block
+ *                     calls get_type() before it replaces them).  Allele bases are upper-cased (ByteArrayAllele::new)
+ *   2. loci           the sorted union of the haplotypes' event starts (:361-408) inside the closed window
+ *                     (haplotype_caller_genotyping_engine.rs:148)
+ *   3. events there   get_overlapping_events (event_map.rs:429-464; a deletion ending here gives way to an insertion here), the
+ *                     first occurrence in haplotype order by (start, alleles) (assembly_based_caller_utils.rs:633-658); an event
+ *                     that starts before the locus becomes (reference base, '*') (replace_span_dels, :726-751); with
+ *                     include_spanning_events == 0 only the events that start at the locus
+ *   4. merged context simple_merge as make_merged_variant_context calls it (src/model/variant_context_utils.rs:379-553, :792-916):
+ *                     the longest reference allele, every alt extended by the reference's extra tail ('*' is not), alleles in
+ *                     first-seen order behind the reference, the span of the longest context.  The priority sort leaves the
+ *                     (haplotype) order as it is; events of one haplotype keep their start order
+ *   5. allele map     create_allele_mapper (assembly_based_caller_utils.rs:720-840), every branch: no overlapping event -> the
+ *                     reference; an event starting here -> its (extended) alt's index, none (-1) if the set does not hold it; an
+ *                     event that started earlier -> '*' if present, else the reference, and stop; spanning off -> reference, stop
+ *   6. window         event_start / event_end = the merged span through expand_within_contig(overlap_margin, contig length)
+ *                     (src/utils/simple_interval.rs:137-147): what phmm_genotype_likelihoods calls "already widened"
+ * Inputs, per region g:
+ *   region_ref_off [n_regions+1], ref_bases   the padded reference bases;  region_ref_start = ref_loc.start
+ *   region_window_start / _end                the closed active_region_window;  region_contig_length  the contig's length
+ *   region_hap_off [n_regions+1]; hap_off [n_haps+1], hap_bases; hap_cigar_off [n_haps+1], hap_cigar (BAM-encoded, as
+ *   phmm_calculate_cigar writes and phmm_project_to_reference reads); hap_start_wrt_ref [n_haps]   the haplotypes in order
+ *   max_mnp_distance (--max-mnp-distance, default 0), include_spanning_events (not --disable-spanning-event-genotyping),
+ *   overlap_margin (--allele-informative-reads-overlap-margin, default 2)
+ * Outputs, dense over all regions, regions in order, loci ascending inside a region -- they pass AS THEY ARE into
+ * phmm_genotype_likelihoods, phmm_allele_frequency, phmm_assign_genotypes and phmm_annotate_events:
+ *   region_event_off [n_regions+1]; region_status [n_regions]
+ *   event_region, event_start, event_end, event_loc, vc_start, vc_end (the unwidened span), event_flags   [capacity[0]]
+ *   event_allele_off [capacity[0]+1];  event_hap_allele [capacity[3]]: per event Nh(region) entries, -1 = none
+ *   allele_length, allele_kind (PHMM_AF_KIND_PLAIN / _SPAN_DEL) [capacity[1]]; allele_bases_off [capacity[1]+1];
+ *   allele_bases [capacity[2]]   ('*' is the one byte '*', length 1)
+ *   optional (hap_event_off NULL skips all seven): the haplotypes' own event maps, dense in haplotype order --
+ *   hap_event_off [n_haps+1]; hap_event_start / _end / _ref_length / _type (PHMM_EV_TYPE_*, the cached type) [capacity[4]];
+ *   hap_event_alt_off [capacity[4]+1]; hap_event_alt [capacity[5]].  The event's reference allele is hap_event_ref_length
+ *   reference bases from hap_event_start.  A region with a negative status has none.
+ * PHMM_EV_HAP_IN_TWO_ALLELES (event_flags): create_allele_mapper pushed some haplotype into two allele lists; event_hap_allele
+ * holds the first one and the caller treats the event on the host.  As written the reference stops at the first event that
+ * starts before the locus and an event map holds one event per start, so no input sets it; the flag stays in the contract.
+ * region_status follows the convention above: 0, or negative where the reference panics or returns Err -- then the region has
+ * no events and the other regions are unaffected.  The first failing haplotype, in the order the reference meets the failures:
+ *   PHMM_EV_STATUS_BAD_OPERATOR   N / P / H in a CIGAR;  PHMM_EV_STATUS_CIGAR_OVERRUN  a CIGAR indexes past the reference or
+ *   the haplotype (only where the reference indexes: a deletion at ref_pos == 0 reads nothing);  PHMM_EV_STATUS_BLOCK  an
+ *   assertion of make_block (two insertions at one start, ...);  PHMM_EV_STATUS_ALLELES  an event whose alleles are equal once
+ *   upper-cased ('a' against 'A': build_event_maps_for_haplotypes returns Err);  PHMM_EV_STATUS_MERGE  simple_merge fails at a
+ *   locus: the merged set has no reference allele left (an alt equals the longest reference), or reference alleles of equal
+ *   length differ -- which one reference array per region cannot produce.
+ * Capacity: capacity[6] = room for events, alleles, allele bytes, map entries, haplotype events, haplotype alt bytes (the last
+ * two are read only with hap_event_off).  If one is too small the call returns PHMM_ERR_EVENT_CAPACITY with the six sizes it
+ * needs in required[6] and writes nothing else; a call with all capacities 0 is the cheap way to ask.  required is written on
+ * success too.  Always sufficient, with E_g = min(reference bases, sum over the haplotypes of bases + CIGAR elements) of region
+ * g: events sum E_g; map entries sum E_g Nh_g; alleles sum E_g (1 + 2 Nh_g); allele bytes alleles x (longest reference +
+ * longest haplotype + 1); haplotype events and alt bytes: sum over the haplotypes of bases + CIGAR elements.  That bound is a
+ * limit, not a way to call: the staging buffer, its pinned mirror and the copy back all have the size of the capacities, so
+ * ask first and pass what required holds.
+ * Footprint: device memory and pinned host memory for the inputs and for the outputs at their capacities; on the device alone,
+ * kept by the handle until phmm_destroy, a workspace of 25 bytes per haplotype base and CIGAR element (plus 200 per haplotype)
+ * and 16 bytes per reference base -- about 70 MB for 1 024 regions of 8 haplotypes of 300 bases.
+ * Out of scope, the caller's: remove_alt_alleles_if_too_many_genotypes (an event whose phmm_genotype_count(ploidy, A_e) exceeds
+ * 1 024 is emitted as it is), given alleles (GGA mode), phasing, reverse_trim_alleles.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): a required array NULL (hap_event_off
+ * non-NULL makes the other six map outputs required), offsets that do not start at 0 or are not monotonic, more than PHMM_EVENTS_MAX_REF reference bases or PHMM_EVENTS_MAX_HAPS haplotypes in a region, a contig length of 0,
+ * a position from 2^62 on, a base outside "ACGTNacgtnRYKMSWBDHVU" (what the reference's allele constructor takes without
+ * making a symbolic allele), a CIGAR element with an operator above 8 or length 0, haplotype bases + CIGAR elements + 8 per
+ * haplotype reaching 2^31 in the call (the workspace is indexed in 32 bits).  n_regions == 0 and regions without haplotypes are fine.  Results are identical from run to run and
+ * whatever the batch.  One thread per handle.
+ */
+#define PHMM_EVENTS_MAX_REF 16384u
+#define PHMM_EVENTS_MAX_HAPS 512u
+#define PHMM_EV_HAP_IN_TWO_ALLELES 1u
+#define PHMM_EV_TYPE_SNP 1
+#define PHMM_EV_TYPE_MNP 2
+#define PHMM_EV_TYPE_INDEL 3
+#define PHMM_EV_STATUS_BAD_OPERATOR (-1)
+#define PHMM_EV_STATUS_BLOCK (-2)
+#define PHMM_EV_STATUS_MERGE (-3)
+#define PHMM_EV_STATUS_CIGAR_OVERRUN (-4)
+#define PHMM_EV_STATUS_ALLELES (-5)
+int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
+                         const uint64_t *region_ref_start, const uint64_t *region_window_start, const uint64_t *region_window_end,
+                         const uint64_t *region_contig_length, const uint32_t *region_hap_off, const uint32_t *hap_off,
+                         const uint8_t *hap_bases, const uint32_t *hap_cigar_off, const uint32_t *hap_cigar,
+                         const uint32_t *hap_start_wrt_ref, uint32_t max_mnp_distance, int include_spanning_events,
+                         uint32_t overlap_margin, const uint32_t *capacity, uint32_t *required, uint32_t *region_event_off,
+                         int32_t *region_status, uint32_t *event_region, uint32_t *event_allele_off, int64_t *event_start,
+                         int64_t *event_end, int64_t *event_loc, int64_t *vc_start, int64_t *vc_end, uint32_t *event_flags,
+                         int32_t *event_hap_allele, uint32_t *allele_length, uint8_t *allele_kind, uint32_t *allele_bases_off,
+                         uint8_t *allele_bases, uint32_t *hap_event_off, int64_t *hap_event_start, int64_t *hap_event_end,
+                         uint32_t *hap_event_ref_length, uint32_t *hap_event_alt_off, uint8_t *hap_event_alt,
+                         uint32_t *hap_event_type);
 
 /*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).

@@ -34,6 +34,7 @@ pub const PHMM_ERR_NOT_BOUND: c_int = 5;
 pub const PHMM_ERR_NO_MEMORY: c_int = 6;
 pub const PHMM_ERR_INTERNAL: c_int = 7;
 pub const PHMM_ERR_CIGAR_CAPACITY: c_int = 8;
+pub const PHMM_ERR_EVENT_CAPACITY: c_int = 9;
 
 /// `overhang_strategy` of `phmm_sw_align` == gkl::smithwaterman::OverhangStrategy
 pub const PHMM_SW_SOFTCLIP: c_int = 0;
@@ -95,6 +96,18 @@ pub const PHMM_GT_SAMPLE_REF_ONLY: c_uint = 4;
 pub const PHMM_ANN_NO_AD: c_uint = 1;
 pub const PHMM_ANN_NO_QD: c_uint = 2;
 pub const PHMM_ANN_QD_JITTER: c_uint = 4;
+/// `phmm_discover_events`: limits per region, the event flag, the cached event types, region statuses
+pub const PHMM_EVENTS_MAX_REF: c_uint = 16384;
+pub const PHMM_EVENTS_MAX_HAPS: c_uint = 512;
+pub const PHMM_EV_HAP_IN_TWO_ALLELES: c_uint = 1;
+pub const PHMM_EV_TYPE_SNP: c_int = 1;
+pub const PHMM_EV_TYPE_MNP: c_int = 2;
+pub const PHMM_EV_TYPE_INDEL: c_int = 3;
+pub const PHMM_EV_STATUS_BAD_OPERATOR: c_int = -1;
+pub const PHMM_EV_STATUS_BLOCK: c_int = -2;
+pub const PHMM_EV_STATUS_MERGE: c_int = -3;
+pub const PHMM_EV_STATUS_CIGAR_OVERRUN: c_int = -4;
+pub const PHMM_EV_STATUS_ALLELES: c_int = -5;
 
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
 /// (src/reads/alignment_utils.rs:52-58, src/model/allele_likelihoods.rs:17)
@@ -699,12 +712,57 @@ extern "C" {
         qd: *mut f64,
         flags: *mut u32,
     ) -> c_int;
+    /// the head of assign_genotype_likelihoods (haplotype_caller_genotyping_engine.rs:125-229): the haplotypes' event maps,
+    /// the loci, the merged alleles and the haplotype -> allele map of every event, dense, as the four calls above take them
+    pub fn phmm_discover_events(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_ref_start: *const u64,
+        region_window_start: *const u64,
+        region_window_end: *const u64,
+        region_contig_length: *const u64,
+        region_hap_off: *const u32,
+        hap_off: *const u32,
+        hap_bases: *const u8,
+        hap_cigar_off: *const u32,
+        hap_cigar: *const u32,
+        hap_start_wrt_ref: *const u32,
+        max_mnp_distance: u32,
+        include_spanning_events: c_int,
+        overlap_margin: u32,
+        capacity: *const u32,
+        required: *mut u32,
+        region_event_off: *mut u32,
+        region_status: *mut i32,
+        event_region: *mut u32,
+        event_allele_off: *mut u32,
+        event_start: *mut i64,
+        event_end: *mut i64,
+        event_loc: *mut i64,
+        vc_start: *mut i64,
+        vc_end: *mut i64,
+        event_flags: *mut u32,
+        event_hap_allele: *mut i32,
+        allele_length: *mut u32,
+        allele_kind: *mut u8,
+        allele_bases_off: *mut u32,
+        allele_bases: *mut u8,
+        hap_event_off: *mut u32,
+        hap_event_start: *mut i64,
+        hap_event_end: *mut i64,
+        hap_event_ref_length: *mut u32,
+        hap_event_alt_off: *mut u32,
+        hap_event_alt: *mut u8,
+        hap_event_type: *mut u32,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "cigar=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

@@ -7,4 +7,5 @@ creating an engine does (there is no CPU fallback).
 """
 from .batch import Read, RegionBatch  # noqa: F401
 from .engine import HipPairHMMEngine, PhmmError  # noqa: F401
+from .events import discover_events  # noqa: F401
 from .genotype import annotate_events, allele_frequency, assign_genotypes, genotype_likelihoods  # noqa: F401

@@ -26,6 +26,7 @@ PHMM_ERR_NOT_BOUND = 5
 PHMM_ERR_NO_MEMORY = 6
 PHMM_ERR_INTERNAL = 7
 PHMM_ERR_CIGAR_CAPACITY = 8
+PHMM_ERR_EVENT_CAPACITY = 9
 PHMM_SW_SOFTCLIP, PHMM_SW_INDEL, PHMM_SW_LEADING_INDEL, PHMM_SW_IGNORE = 0, 1, 2, 3
 PHMM_SW_NO_REFERENCE = 0xffffffff
 PHMM_PROJECT_REALIGNED, PHMM_PROJECT_UNCHANGED = 0, 1
@@ -36,6 +37,10 @@ PHMM_AF_ALLELE_PLAUSIBLE, PHMM_AF_ALLELE_OUTPUT = 1, 2
 PHMM_GT_USE_PLS, PHMM_GT_USE_POSTERIORS = 0, 1
 PHMM_GT_SAMPLE_UNINFORMATIVE, PHMM_GT_SAMPLE_NON_REF_BEST, PHMM_GT_SAMPLE_REF_ONLY = 1, 2, 4
 PHMM_ANN_NO_AD, PHMM_ANN_NO_QD, PHMM_ANN_QD_JITTER = 1, 2, 4
+PHMM_EVENTS_MAX_REF, PHMM_EVENTS_MAX_HAPS = 16384, 512
+PHMM_EV_HAP_IN_TWO_ALLELES = 1
+PHMM_EV_TYPE_SNP, PHMM_EV_TYPE_MNP, PHMM_EV_TYPE_INDEL = 1, 2, 3
+PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
 
 class EngineConfig(C.Structure):
     """phmm_engine_config (include/phmm.h)."""
@@ -140,6 +145,11 @@ SYMBOLS = [
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), u8p, f64p, u32p, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), f64p, u32p, u8p, u8p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        f64p, u32p]),
+    ("phmm_discover_events", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
+                                       C.c_uint32, C.c_int, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_int32), u32p, u32p,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), u32p, C.POINTER(C.c_int32), u32p, u8p, u32p, u8p, u32p,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), u32p, u32p, u8p, u32p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),

@@ -16,6 +16,7 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "genotype": ("phmm_genotype_internal.hpp", "phmm_genotype_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip",
                  "phmm_annotate_internal.hpp", "phmm_annotate_kernels.hip", "phmm_assign_internal.hpp",
                  "phmm_assign_kernels.hip"),
+    "events": ("phmm_events_internal.hpp", "phmm_events_kernels.hip"),
 }
 
 
