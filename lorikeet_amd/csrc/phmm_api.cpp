@@ -1,4 +1,4 @@
-// C ABI (include/phmm.h) + launch planner of the MI355X PairHMM engine.
+// C ABI (include/phmm.h) of the MI355X PairHMM engine: the launch planner is phmm_plan.cpp, this file places its plans and launches them.
 //
 // Host side of the drop-in boundary: takes the flattened (reads, haplotypes, quals) of any number
 // of assembly regions, bins the regions into kernel shape classes <L lanes per pair, K haplotype
@@ -20,7 +20,6 @@
 #include <deque>
 #include <map>
 #include <memory>
-#include <tuple>
 #include <unordered_map>
 #include <mutex>
 #include <string>
@@ -34,17 +33,14 @@
 #include "phmm_staging.hpp"
 #include <sched.h>
 #include "phmm_internal.hpp"
+#include "phmm_plan.hpp"
 #include "phmm_tables.hpp"
 
 using namespace phmm;
 using namespace phmm_host;
+using namespace phmm_plan;
 
 namespace {
-
-#ifndef PHMM_MIXED_RUNS
-#define PHMM_MIXED_RUNS 32
-#endif
-constexpr unsigned kMixedRunsPerSlot = PHMM_MIXED_RUNS;  // runs per wave slot of a mixed batch (see the planner)
 
 std::mutex g_err_mu;
 std::string g_create_err = "";
@@ -58,10 +54,6 @@ std::atomic<int> g_user_handles[kMaxDevices];
 std::mutex g_backing_mu;
 std::map<std::pair<int, unsigned>, phmm_handle *> g_backing;
 
-constexpr size_t kLdsBytesPerCU = 160 * 1024;
-constexpr size_t kLdsRowBytes = 72;  // sizeof(RowConst) in phmm_kernels.hip
-constexpr uint32_t kNumSimd = 256 * 4;
-constexpr uint64_t kGenericScratchBytes = 1ull << 30;
 // Chunked host path: batches whose per-base arrays exceed kOneShotBytes are cut into chunks of regions whose arrays grow
 // from kFirstChunkBytes (the GPU starts early) to kChunkBytes (large launches are the efficient ones).  Measured on
 // config-2 batches, one shot vs chunked: 32 regions 548 -> 479 us, 256 regions 4.36 -> 3.13 ms, 4096 regions 43.2 ms with
@@ -78,35 +70,6 @@ static const int kForcedEagerD2H = getenv("PHMM_EAGER_D2H") ? atoi(getenv("PHMM_
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-struct ShapeClass {
-    int L = 0, K = 0;  // L == 0 -> generic kernel
-    std::vector<uint32_t> reads;  // global read indices (host copy; uploaded unless identity)
-    bool identity = false;        // reads == 0..n-1
-    uint32_t max_r = 0, max_h = 0, max_quads = 0;
-    uint64_t cells = 0;
-    // launch configuration
-    uint32_t lds_rows = 8;
-    int waves_per_block = MAX_WAVES_PER_BLOCK;
-    size_t lds_bytes = 0;
-    dim3 grid;
-    // chained class: items are (region, haplotype group, run of reads) instead of single reads
-    bool chain = false;
-    std::vector<uint32_t> regions;  // member regions (chain classes)
-    std::vector<ChainItem> chain_items;  // host side; launched as part of its ChainGroup
-    uint32_t cnd_select = 0;
-    int streams = 1;  // chained classes: sub-runs swept side by side (phmm_chain_kernels.hip)
-    bool f32_first = false;  // chained class at 16 lanes per pair of a PHMM_FLAG_F32_FIRST handle: f32 sweep, then the
-                             // f64 per-read kernel over the reads it flagged (the per-read launch geometry is filled in too)
-    // device
-    uint32_t *d_reads = nullptr;
-    // generic only
-    std::vector<uint64_t> pair_first;
-    uint64_t *d_pair_first = nullptr;
-    double *d_scratch = nullptr;
-    uint32_t generic_blocks = 0;
-    char name[48] = {0};
-};
-
 }  // namespace
 
 void phmm_host::set_create_error(const std::string &msg) {
@@ -116,19 +79,15 @@ void phmm_host::set_create_error(const std::string &msg) {
 
 struct phmm_batch {
     phmm_handle *h = nullptr;
-    uint32_t n_regions = 0, n_reads = 0, n_haps = 0;
     uint64_t n_out = 0, read_bytes = 0, hap_bytes = 0;
-    uint64_t cells = 0, alg_bytes = 0;
-    std::vector<ShapeClass> classes;
-    // every chained f64 class of one lanes-per-pair value goes out in ONE launch (phmm_chain_kernels.hip)
-    struct ChainGroup {
-        int L = 0;
-        bool f32 = false;  // the f32 sweep of a PHMM_FLAG_F32_FIRST handle (the f64 per-read redo follows per class)
-        int single_k = 0;  // the K all items share (per-K kernel), 0 = mixed (any-K kernel)
-        std::vector<ChainItem> items;
-        ChainItem *d_items = nullptr;
+    BatchPlan plan;  // what is launched (phmm_plan.hpp); below: where it lives on the device
+    struct ClassDevice {  // of plan.classes[i]
+        uint32_t *reads = nullptr;       // null: identity, or a chained class without a per-read kernel behind it
+        uint64_t *pair_first = nullptr;  // generic only
+        double *scratch = nullptr;       // generic only
     };
-    std::vector<ChainGroup> chain_groups;
+    std::vector<ClassDevice> class_dev;
+    std::vector<ChainItem *> d_group_items;  // of plan.chain_groups[i]
     // device metadata (one allocation)
     uint32_t *d_read_region = nullptr, *d_region_read_off = nullptr, *d_region_hap_off = nullptr, *d_read_off = nullptr,
              *d_hap_off = nullptr, *d_status = nullptr;
@@ -145,73 +104,19 @@ struct phmm_batch {
     size_t out_arena_off = 0;     // arena mode: offset of [status word | out]
     bool tight_out = true;        // out_off has no gaps (every slot is written by a kernel)
     std::vector<std::pair<uint64_t, uint64_t>> out_extents;  // !tight_out: (first slot, Nr*Nh) per region -- gaps stay untouched
-    uint32_t max_h = 0;           // longest haplotype (sizes the scratch of phmm_rescue)
     double *rescue_scratch = nullptr;  // non-null: the exact pass rides behind every launch (persistent batches: own
                                        // scratch; engine-level call: the arena's, its results are consumed on the device)
     uint32_t rescue_blocks = 0;
     bool bound = false;
-    std::string dominant;
-    uint64_t pad_column_cells = 0, pad_slot_cells = 0;  // ... of which columns beyond a haplotype's end / haplotype slots left empty
-    uint64_t swept_cells = 0;  // lane-cells the planned launches sweep: every row of every wave x 64 lanes x its K columns, padding
-                               // columns, empty haplotype slots and all (phmm_batch_executed_cells)
 };
-
-namespace {
 
 #define HIP_TRY(h, call, ret)                  \
     do {                                       \
         if (!hip_ok((h), (call), #call)) return ret; \
     } while (0)
 
-int round_up_k(int k) {
-    for (int i = 0; i < kNumInstantiatedK; ++i)
-        if (kInstantiatedK[i] >= k) return kInstantiatedK[i];
-    return 0;
-}
-
-// Registers cap the resident waves per SIMD (3*K f64 of DP state per lane dominates; K <= 25 is
-// compiled for 2 waves, PHMM_TWO_WAVE_MAX_K).
-int waves_per_simd(int K) { return K <= 25 ? 2 : 1; }
-
-// Throughput model of a region under <L,K>, calibrated on MI355X (tools/shapes.py): useful fraction of
-// issued lane-steps x the per-step overhead (DPP shifts, LDS fetch, loop: ~11 of 7*K+11 VALU ops per
-// step) x the issue rate one resident wave reaches alone (a wave issues a VALU op every ~6 clk, two waves
-// together one every ~4.7: tools/ubench/issue.hip; measured 0.81 on <16,25>).
-// Chained kernel at 16 lanes per pair: the four haplotype slots of a wave can be shared by S = 1, 2 or 4 streams of
-// reads (phmm_chain_kernels.hip), so any haplotype count fills them.  Every extra stream costs row-producer work
-// (rows are built per stream, in shorter ticks): measured 3990 / 3700 / 3300 GCUPS at 1 / 2 / 4 streams with all
-// slots busy, i.e. ~6 % per extra stream.  Returns S, and the slot fill (times that factor) it achieves.
-int chain_streams(uint32_t nh, double *fill_out) {
-    int best_s = 1;
-    double best = 0.0;
-    for (int S : {1, 2, 4}) {
-        const uint32_t gs = 4 / S;
-        const double fill = (double)nh / (double)(((nh + gs - 1) / gs) * gs) * (1.0 - 0.06 * (S - 1));
-        if (fill > best + 1e-9) {
-            best = fill;
-            best_s = S;
-        }
-    }
-    if (fill_out) *fill_out = best;
-    return best_s;
-}
-
-double shape_efficiency(int L, int K, uint32_t nh, uint32_t mean_r, uint32_t max_h, bool chained) {
-    const int G = WAVE / L;
-    double hap_fill = (double)nh / (double)(((nh + G - 1) / G) * G);
-    if (chained && L == 16) (void)chain_streams(nh, &hap_fill);
-    // fill / drain steps of the lane pipeline: per read, or (chained kernel) amortised over a run of reads
-    const double ramp = chained ? 1.0 : (double)std::max<uint32_t>(mean_r, 1) / (double)(std::max<uint32_t>(mean_r, 1) + L - 1);
-    const double col_fill = (double)max_h / (double)(L * K);
-    const double step = 7.0 * K / (7.0 * K + 11.0);
-    const double occ = waves_per_simd(K) >= 2 ? 1.0 : 0.84;
-    return hap_fill * ramp * col_fill * step * occ;
-}
-
-}  // namespace
-
 // The one place the PHMM_* developer switches are read (phmm_set_switch changes them per handle afterwards): phmm_create,
-// and phmm_plan_describe for its host-only handle, so that a described plan is the plan an engine of this process makes.
+// and phmm_plan_describe, so that a described plan is the plan an engine of this process makes.
 static void read_env_switches(Switches &w) {
     auto env = [](const char *name, int &dst) {
         if (const char *e = getenv(name)) dst = atoi(e);
@@ -507,11 +412,139 @@ const char *validate_offsets(uint32_t n_regions, const uint32_t *region_read_off
 
 }  // namespace phmm_host
 
-// (`dry`: plan only -- no device is touched, every "device" pointer of the batch stays null: phmm_plan_describe)
+namespace {
+
+// ---- device memory provider (after planning: the arena is sized from the plan) -----------------
+// arena mode: bump-allocate from the handle's arena, "uploads" go to the pinned mirror and travel in
+// one copy later; otherwise hipMalloc per piece and async copies on the handle's stream.
+// (the first failure latches: every later call does nothing)
+struct Placer {
+    phmm_handle *h;
+    phmm_batch *b;
+    bool ok = true;
+    bool async_pending = false;
+    void *dalloc(size_t bytes, void **mirror) {
+        if (mirror) *mirror = nullptr;
+        if (!ok) return nullptr;
+        if (b->arena && align_up(b->arena->used, 256) + bytes <= b->arena->cap) {
+            const size_t off = align_up(b->arena->used, 256);
+            b->arena->used = off + bytes;
+            if (mirror) *mirror = b->arena->host + off;
+            return b->arena->dev + off;
+        }
+        void *p = nullptr;
+        ok = hip_ok(h, hipMalloc(&p, std::max<size_t>(bytes, 256)), "hipMalloc(batch)");
+        if (ok) b->mallocs.push_back(p);
+        return p;
+    }
+    void up(void *dst, void *mirror, const void *src, size_t bytes) {
+        if (!ok || !bytes) return;
+        if (mirror) {
+            memcpy(mirror, src, bytes);
+        } else {
+            ok = hip_ok(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->S()), "H2D meta");
+            async_pending = true;
+        }
+    }
+    template <class T>
+    T *put(const T *src, size_t count) {
+        void *mirror;
+        T *dst = (T *)dalloc(count * sizeof(T), &mirror);
+        up(dst, mirror, src, count * sizeof(T));
+        return dst;
+    }
+};
+
+// Places the finished plan of `b` (b->plan) in device memory: offset arrays, per-class lists, redo flags, generic scratch, the
+// status word and rescue scratch of a persistent batch, the items of every chained launch.  Decides nothing about the launches.
+// false: h->err says why; what was allocated on the way is the batch's (b->mallocs).
+bool place_batch(phmm_handle *h, phmm_batch *b, const BatchOffsets &o, bool use_arena, size_t extra_arena_bytes) {
+    const BatchPlan &plan = b->plan;
+    const uint32_t n_regions = plan.n_regions, n_reads = plan.n_reads, n_haps = plan.n_haps;
+    if (use_arena) {
+        // bytes of per-class work lists placed below (the read list of every class: identity and purely chained classes upload none)
+        size_t class_meta = 0;
+        for (const ShapeClass &c : plan.classes) {
+            class_meta += align_up(c.reads.size() * 4, 256);
+            if (!c.L) class_meta += align_up(c.pair_first.size() * 8, 256);
+        }
+        for (const ChainGroup &grp : plan.chain_groups) class_meta += align_up(grp.items.size() * sizeof(ChainItem), 256);
+        // exact: every dalloc() below and the payload / result placement of enqueue_compute (each piece starts on a
+        // 256-byte boundary), so that nothing staged later can fail for lack of room
+        const size_t need = align_up((size_t)n_reads * 4, 256) + align_up((size_t)(n_regions + 1) * 4, 256) * 2 +
+                            align_up((size_t)(n_reads + 1) * 4, 256) + align_up((size_t)(n_haps + 1) * 4, 256) +
+                            align_up((size_t)(n_regions + 1) * 8, 256) + class_meta + 5 * align_up(b->read_bytes, 256) +
+                            align_up(b->hap_bytes, 256) + 256 + align_up(b->n_out * 8, 256) + 4096 + extra_arena_bytes +
+                            align_up((size_t)n_reads, 256) /* redo flags of the f32-first mode */;
+        Arena &A = h->A();
+        if (!canary_before_staging(h, A)) return false;  // (PHMM_MIRROR_CANARY: a store landed in the last call's result block after it returned)
+        if (A.cap < need) {
+            (void)hipStreamSynchronize(h->S());
+            if (A.dev) (void)hipFree(A.dev);
+            if (A.host) (void)hipHostFree(A.host);
+            A.dev = A.host = nullptr;
+            A.cap = 0;
+            const size_t cap = std::max<size_t>(need + need / 2, 1 << 20);
+            if (!hip_ok(h, hipMalloc((void **)&A.dev, cap), "hipMalloc(arena)") ||
+                !hip_ok(h, hipHostMalloc((void **)&A.host, cap, hipHostMallocDefault), "hipHostMalloc(arena)"))
+                return false;
+            A.cap = cap;
+        }
+        A.used = 0;
+        b->arena = &A;
+    }
+    Placer p{h, b};
+
+    // ---- device metadata --------------------------------------------------------------------
+    b->d_read_region = p.put(plan.read_region.data(), n_reads);
+    b->d_region_read_off = p.put(o.region_read_off, (size_t)n_regions + 1);
+    b->d_region_hap_off = p.put(o.region_hap_off, (size_t)n_regions + 1);
+    b->d_read_off = p.put(o.read_off, (size_t)n_reads + 1);
+    b->d_hap_off = p.put(o.hap_off, (size_t)n_haps + 1);
+    b->d_out_off = p.put(o.out_off, (size_t)n_regions + 1);
+    if (!b->arena) {  // persistent batch: own status word (arena mode keeps it next to the results)
+        b->d_status = (uint32_t *)p.dalloc(256, nullptr);
+        if (p.ok) p.ok = hip_ok(h, hipMemsetAsync(b->d_status, 0, 4, h->S()), "memset status");
+        // ... and own scratch for the exact pass, which rides behind the forward kernels of every launch (the caller
+        // owns the stream, so the library cannot look at the status word in between)
+        if (p.ok && n_reads && !h->sw.no_rescue) {
+            size_t bytes = 0;
+            rescue_geometry(plan.max_h, &b->rescue_blocks, &bytes);
+            p.ok = hip_ok(h, hipMalloc((void **)&b->rescue_scratch, bytes), "hipMalloc(rescue scratch)");
+            if (p.ok) b->mallocs.push_back(b->rescue_scratch);
+        }
+    }
+
+    // ---- per-class lists ----------------------------------------------------------------------
+    b->class_dev.resize(plan.classes.size());
+    for (size_t i = 0; i < plan.classes.size(); ++i) {
+        const ShapeClass &c = plan.classes[i];
+        phmm_batch::ClassDevice &d = b->class_dev[i];
+        // the per-read kernel's list of reads (the f64 per-read kernel of an f32-first class runs behind the f32 sweep over the reads it flags)
+        if (!c.identity && (!c.chain || c.f32_first)) d.reads = p.put(c.reads.data(), c.reads.size());
+        if (c.f32_first && !b->d_redo) b->d_redo = (uint8_t *)p.dalloc(align_up((size_t)n_reads, 256), nullptr);
+        if (!c.L) {
+            // scratch can be large: always its own allocation, never the arena
+            if (p.ok) p.ok = hip_ok(h, hipMalloc((void **)&d.scratch, c.generic_scratch_bytes), "hipMalloc(generic scratch)");
+            if (p.ok) b->mallocs.push_back(d.scratch);
+            d.pair_first = p.put(c.pair_first.data(), c.pair_first.size());
+        }
+    }
+    b->d_group_items.resize(plan.chain_groups.size());
+    for (size_t i = 0; i < plan.chain_groups.size(); ++i)
+        b->d_group_items[i] = p.put(plan.chain_groups[i].items.data(), plan.chain_groups[i].items.size());
+    // the caller's offset arrays may die when the call returns: finish the async copies first (arena mode copied into the mirror)
+    if (p.ok && p.async_pending) p.ok = hip_ok(h, hipStreamSynchronize(h->S()), "sync(meta)");
+    return p.ok;
+}
+
+}  // namespace
+
+// Plans a batch (phmm_plan.cpp) and places the plan on the device.
 static phmm_batch *batch_create_impl(phmm_handle *h, uint32_t n_regions, const uint32_t *region_read_off,
                                      const uint32_t *region_hap_off, const uint32_t *read_off,
                                      const uint32_t *hap_off, const uint64_t *out_off, bool use_arena,
-                                     size_t extra_arena_bytes = 0, bool dry = false) {
+                                     size_t extra_arena_bytes = 0) {
     if (!h) return nullptr;
     h->err.clear();
     h->err_code = PHMM_OK;
@@ -523,31 +556,23 @@ static phmm_batch *batch_create_impl(phmm_handle *h, uint32_t n_regions, const u
         return nullptr;
     }
     const uint32_t n_reads = region_read_off[n_regions], n_haps = region_hap_off[n_regions];
-    std::unique_ptr<DeviceGuard> dg;
-    if (!dry) {
-        dg.reset(new DeviceGuard(h->device));
-        if (!dg->ok) {
-            h->err = "hipSetDevice failed";
-            h->err_code = PHMM_ERR_HIP;
-            return nullptr;
-        }
+    DeviceGuard dg(h->device);
+    if (!dg.ok) {
+        h->err = "hipSetDevice failed";
+        h->err_code = PHMM_ERR_HIP;
+        return nullptr;
     }
 
-    // (owned until the plan is complete: an exception on the way -- a host allocation -- releases it and what it holds)
+    // (owned until the plan is placed: an exception on the way -- a host allocation -- releases it and what it holds)
     struct BatchDeleter {
-        bool dry;
         void operator()(phmm_batch *x) const {
-            if (!dry)
-                for (void *m : x->mallocs) (void)hipFree(m);
+            for (void *m : x->mallocs) (void)hipFree(m);
             delete x;
         }
     };
-    std::unique_ptr<phmm_batch, BatchDeleter> owner(new phmm_batch(), BatchDeleter{dry});
+    std::unique_ptr<phmm_batch, BatchDeleter> owner(new phmm_batch());
     phmm_batch *b = owner.get();
     b->h = h;
-    b->n_regions = n_regions;
-    b->n_reads = n_reads;
-    b->n_haps = n_haps;
     b->n_out = out_off[n_regions];
     b->read_bytes = read_off[n_reads];
     b->hap_bytes = hap_off[n_haps];
@@ -557,661 +582,9 @@ static phmm_batch *batch_create_impl(phmm_handle *h, uint32_t n_regions, const u
             b->out_extents.emplace_back(out_off[g], (uint64_t)(region_read_off[g + 1] - region_read_off[g]) *
                                                         (uint64_t)(region_hap_off[g + 1] - region_hap_off[g]));
     b->home_stream = h->S();
-
-    bool ok = true;
-    auto mark_now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double marks[8] = {mark_now()};
-    int n_marks = 1;
-    auto mark = [&]() { if (n_marks < 8) marks[n_marks++] = mark_now(); };
-
-    // ---- per-region shape, totals -----------------------------------------------------------
-    struct RegionShape {
-        uint32_t nr, nh, max_r, max_h, mean_r, min_r = 0xffffffffu, min_h = 0xffffffffu;
-        uint64_t cells;
-    };
-    std::vector<RegionShape> shape(n_regions);
-    std::vector<uint32_t> read_region(n_reads);
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        RegionShape s{};
-        s.nr = region_read_off[g + 1] - region_read_off[g];
-        s.nh = region_hap_off[g + 1] - region_hap_off[g];
-        uint64_t sum_r = 0, sum_h = 0;
-        for (uint32_t r = region_read_off[g]; r < region_read_off[g + 1]; ++r) {
-            const uint32_t len = read_off[r + 1] - read_off[r];
-            s.max_r = std::max(s.max_r, len);
-            s.min_r = std::min(s.min_r, len);
-            sum_r += len;
-            read_region[r] = g;
-        }
-        for (uint32_t a = region_hap_off[g]; a < region_hap_off[g + 1]; ++a) {
-            const uint32_t len = hap_off[a + 1] - hap_off[a];
-            s.max_h = std::max(s.max_h, len);
-            s.min_h = std::min(s.min_h, len);
-            sum_h += len;
-        }
-        s.mean_r = s.nr ? (uint32_t)(sum_r / s.nr) : 0;
-        s.cells = sum_r * sum_h;
-        b->cells += s.cells;
-        b->alg_bytes += 5 * sum_r + sum_h + 8ull * s.nr * s.nh;
-        shape[g] = s;
-    }
-
-    mark();  // 1: shapes
-    // ---- choose <L,K> per region ------------------------------------------------------------
-    // Candidates L in {16,32,64}; K = ceil(max_h / L) rounded up to an instantiated value.
-    // Pick the most efficient one, then trade lanes-per-pair for more waves while the batch is
-    // too small to fill the chip.
-    // The chained kernel holds a 19 KB LDS ring per wave (two waves per SIMD): a win wherever the per-read kernel
-    // runs two waves per SIMD anyway, a loss against the three or four waves small K gets at 32 / 64 lanes per
-    // pair (measured: <32,10> 3150 per-read vs 2860 chained; <32,13> 3030 vs 3450; <32,19> 3220 vs 3470).
-    const Switches &sw = h->sw;
-    const bool chain_forced = sw.force_chain >= 0;  // tests: every chainable shape chains
-    auto chain_shape_ok = [&](int L, int k, const RegionShape &s) {
-        return k > 0 && k <= chain_max_k() && (L == 16 || k >= 13 || chain_forced) && s.min_r >= 1 && s.min_h >= 1 &&
-               s.nh <= 0xffffu /* ChainItem::quad */;
-    };
-    bool assume_chain = false;  // second planning pass: the batch is large enough for the chained kernel
-    auto pick = [&](const RegionShape &s, int min_L, int &L_out, int &K_out) {
-        double best = -1.0;
-        L_out = 0;
-        K_out = 0;
-        for (int L : {16, 32, 64}) {
-            if (L < min_L) continue;
-            if (h->sw.force_L && L != h->sw.force_L) continue;
-            const int k = round_up_k((int)((std::max<uint32_t>(s.max_h, 1) + L - 1) / L));
-            if (!k) continue;
-            const double e = shape_efficiency(L, k, s.nh, s.mean_r, s.max_h, assume_chain && chain_shape_ok(L, k, s));
-            if (e > best) {
-                best = e;
-                L_out = L;
-                K_out = k;
-            }
-        }
-    };
-    std::vector<int> reg_L(n_regions), reg_K(n_regions);
-    int min_L = 16;
-    auto plan_shapes = [&]() {
-        min_L = 16;
-        for (;;) {
-            uint64_t waves = 0;
-            for (uint32_t g = 0; g < n_regions; ++g) {
-                const RegionShape &s = shape[g];
-                if (!s.nr || !s.nh) {
-                    reg_L[g] = reg_K[g] = -1;  // nothing to do
-                    continue;
-                }
-                pick(s, min_L, reg_L[g], reg_K[g]);
-                if (reg_L[g]) waves += (uint64_t)s.nr * ((s.nh + WAVE / reg_L[g] - 1) / (WAVE / reg_L[g]));
-            }
-            // one wave per SIMD is enough to stop trading lanes for waves (measured on 1, 2, 4 regions of config 2:
-            // <64,5> 41 us, <32,10> 54 us vs <64,5> 60 us, <16,19> 87 us vs <32,10> 88 us)
-            if (waves * h->gpu_sharers >= 1ull * kNumSimd || min_L == 64 || h->sw.force_L) break;
-            min_L *= 2;
-        }
-    };
-    plan_shapes();
-
-    // Chained kernel (phmm_chain_kernels.hip): reads of a region stream back to back through the lane
-    // pipeline, which removes the per-read fill/drain steps.  Worth it (and balanced) only when there is
-    // enough work to give every wave a run of reads: decide per batch, qualify per region.
-    const int force_streams = sw.force_streams;  // tests: 1 | 2 | 4
-    auto streams_of = [&](uint32_t g) {
-        if (reg_L[g] != 16) return 1;
-        if (force_streams == 1 || force_streams == 2 || force_streams == 4) return force_streams;
-        return chain_streams(shape[g].nh, nullptr);
-    };
-    auto count_units = [&]() {  // wave-sweeps (one read against one wave-load of haplotypes) under the chosen shapes
-        uint64_t u = 0;
-        for (uint32_t g = 0; g < n_regions; ++g)
-            if (reg_L[g] > 0) {
-                const uint32_t S = (uint32_t)streams_of(g), gs = (uint32_t)(WAVE / reg_L[g]) / S;
-                u += (uint64_t)shape[g].nr * ((shape[g].nh + gs - 1) / gs) / S;
-            }
-        return u;
-    };
-    uint64_t units = count_units();
-    // run length: about eight runs per wave slot (balance), but never runs shorter than four reads (measured on 128
-    // regions of config 2: runs of 2 reads 3380, of 4 reads 3530, per-read kernel 3450 GCUPS); below two runs of two
-    // per slot the batch stays with the per-read kernel
-    auto runs_for = [&](uint64_t u) {
-        const uint32_t r = (uint32_t)std::min<uint64_t>(CHAIN_MAX_READS, u / (8ull * 2 * kNumSimd));
-        return r >= 2 && r < 4 ? 4u : r;
-    };
-    uint32_t chain_reads = runs_for(units);
-    if (chain_forced) chain_reads = (uint32_t)std::min(CHAIN_MAX_READS, sw.force_chain);
-    if (chain_reads >= 2 && !h->sw.force_L) {
-        // chained sweeps pay no per-read fill/drain: choose the shapes again without that term (more lanes per pair
-        // become attractive for regions with few haplotypes), and keep the result if the batch still chains
-        std::vector<int> L0 = reg_L, K0 = reg_K;
-        assume_chain = true;
-        plan_shapes();
-        const uint32_t cr = chain_forced ? chain_reads : runs_for(count_units());
-        if (cr >= 2 && min_L == 16) {
-            chain_reads = cr;
-            units = count_units();
-        } else {
-            reg_L = L0;
-            reg_K = K0;
-        }
-        assume_chain = false;
-    }
-    auto chainable = [&](uint32_t g) {
-        const RegionShape &s = shape[g];
-        return chain_reads >= 2 && reg_L[g] > 0 && chain_shape_ok(reg_L[g], reg_K[g], s);
-    };
-
-    if (sw.trace)
-        fprintf(stderr, "phmm plan: %u regions, min_L %d, units %llu, chain_reads %u, region0 <%d,%d> chainable %d\n", n_regions,
-                min_L, (unsigned long long)units, chain_reads, n_regions ? reg_L[0] : 0, n_regions ? reg_K[0] : 0,
-                n_regions ? (int)chainable(0) : 0);
-    mark();  // 2: <L,K> choice
-    std::map<std::tuple<int, int, int>, ShapeClass> by_shape;  // (L, K, 0 = per-read kernel | streams of the chained kernel)
-    for (uint32_t g = 0; g < n_regions; ++g) {
-        if (reg_L[g] < 0) continue;
-        const RegionShape &s = shape[g];
-        int L = reg_L[g], K = reg_K[g];
-        // LDS staging must hold the longest read of the region, one wave per block at least
-        const size_t rows = align_up((size_t)s.max_r + 1, 8);
-        if (L && rows * kLdsRowBytes > kLdsBytesPerCU) L = K = 0;
-        const bool chain = L && chainable(g);
-        const int streams = chain ? streams_of(g) : 1;
-        ShapeClass &c = by_shape[std::make_tuple(L, K, chain ? streams : 0)];
-        c.L = L;
-        c.K = K;
-        c.chain = chain;
-        c.streams = streams;
-        if (chain) c.regions.push_back(g);
-        for (uint32_t r = region_read_off[g]; r < region_read_off[g + 1]; ++r) c.reads.push_back(r);
-        c.max_r = std::max(c.max_r, s.max_r);
-        c.max_h = std::max(c.max_h, s.max_h);
-        if (L) c.max_quads = std::max(c.max_quads, (s.nh + WAVE / L - 1) / (WAVE / L));
-        c.cells += s.cells;
-        if (!L)
-            for (uint32_t r = region_read_off[g]; r < region_read_off[g + 1]; ++r) c.pair_first.push_back(s.nh);
-    }
-
-    // Reads per run.  Uniform batches get `chain_reads` (about eight runs per wave slot), mixed ones a quarter of that (below).
-    // Scaling a region's count by its cost per read -- (rows + SUM + RESET) x (7 VALU per column + ~11 per step) relative to
-    // the batch's mean, so that every work item costs about the same -- looked right and measured wrong once the items were
-    // sorted by cost and spread over the XCDs (1 536 mixed regions: 17.4 ms with it, 16.8 without): short runs of expensive
-    // reads pay the pipeline's fill more often than they save at the tail.  PHMM_COST_SCALED_RUNS builds it back in (A/B).
-    std::vector<uint32_t> reg_run(n_regions, 0);
-    {
-#ifdef PHMM_COST_SCALED_RUNS
-        auto read_cost = [&](uint32_t g, int K) { return (double)(shape[g].mean_r + 2) * (7.0 * K + 11.0); };
-        double cost_sum = 0.0, unit_sum = 0.0;
-        for (const auto &kv : by_shape)
-            if (kv.second.chain)
-                for (uint32_t g : kv.second.regions) {
-                    const uint32_t gs = (uint32_t)(WAVE / kv.second.L) / (uint32_t)kv.second.streams;
-                    const double u = (double)shape[g].nr * ((shape[g].nh + gs - 1) / gs) / kv.second.streams;
-                    cost_sum += u * read_cost(g, kv.second.K);
-                    unit_sum += u;
-                }
-        const double mean_cost = unit_sum > 0 ? cost_sum / unit_sum : 1.0;
-#endif
-        // A uniform batch balances with eight equal runs per wave slot; a mix of classes does not -- its items differ in
-        // cost whatever the estimate, and the launch ends when the last long item does.  Mixed batches therefore get runs
-        // a quarter as long (32 per slot, never below 4 reads): 1 536 mixed regions 20.4 -> 16.9 ms.
-        size_t n_chain_classes = 0;
-        for (const auto &kv : by_shape) n_chain_classes += kv.second.chain ? 1 : 0;
-        uint32_t base_reads = chain_reads;
-        if (n_chain_classes > 1 && !chain_forced)
-            base_reads = std::max<uint32_t>(4, std::min<uint32_t>(chain_reads, (uint32_t)(units / ((uint64_t)kMixedRunsPerSlot * 2 * kNumSimd))));
-        for (const auto &kv : by_shape)
-            if (kv.second.chain)
-                for (uint32_t g : kv.second.regions) {
-                    double r = base_reads;
-#ifdef PHMM_COST_SCALED_RUNS
-                    if (!chain_forced) r = std::min<double>(CHAIN_MAX_READS, std::max(4.0, r * mean_cost / read_cost(g, kv.second.K) + 0.5));
-#endif
-                    reg_run[g] = std::min<uint32_t>(CHAIN_MAX_READS, (uint32_t)r * (uint32_t)kv.second.streams);
-                }
-    }
-    // bytes of per-class work lists the plan will place in device memory
-    size_t class_meta = 0;
-    for (const auto &kv : by_shape) {
-        const ShapeClass &c = kv.second;
-        b->max_h = std::max(b->max_h, c.max_h);
-        class_meta += align_up(c.reads.size() * 4, 256);
-        if (c.chain) {
-            const uint32_t gs = (uint32_t)(WAVE / c.L) / (uint32_t)c.streams;
-            uint64_t items = 0;
-            for (uint32_t g : c.regions)
-                items += (uint64_t)((shape[g].nh + gs - 1) / gs + 3) * ((shape[g].nr + reg_run[g] - 1) / reg_run[g]);  // (+ 3: a remainder in items of its own, below)
-            class_meta += align_up(items * sizeof(ChainItem), 256);
-        }
-        if (!c.L) class_meta += align_up((c.pair_first.size() + 1) * 8, 256);
-    }
-    mark();  // 3: classes, run lengths
-    // ---- device memory provider (after planning: the arena is sized from the plan) -----------------
-    // arena mode: bump-allocate from the handle's arena, "uploads" go to the pinned mirror and travel in
-    // one copy later; otherwise hipMalloc per piece and async copies on the handle's stream.
-    if (use_arena) {
-        // exact: every dalloc() below and the payload / result placement of enqueue_compute (each piece starts on a
-        // 256-byte boundary), so that nothing staged later can fail for lack of room
-        const size_t need = align_up((size_t)n_reads * 4, 256) + align_up((size_t)(n_regions + 1) * 4, 256) * 2 +
-                            align_up((size_t)(n_reads + 1) * 4, 256) + align_up((size_t)(n_haps + 1) * 4, 256) +
-                            align_up((size_t)(n_regions + 1) * 8, 256) + class_meta + 5 * align_up(b->read_bytes, 256) +
-                            align_up(b->hap_bytes, 256) + 256 + align_up(b->n_out * 8, 256) + 4096 + extra_arena_bytes +
-                            align_up((size_t)n_reads, 256) /* redo flags of the f32-first mode */;
-        Arena &A = h->A();
-        if (!canary_before_staging(h, A)) return nullptr;  // (PHMM_MIRROR_CANARY: a store landed in the last call's result block after it returned)
-        if (A.cap < need) {
-            (void)hipStreamSynchronize(h->S());
-            if (A.dev) (void)hipFree(A.dev);
-            if (A.host) (void)hipHostFree(A.host);
-            A.dev = A.host = nullptr;
-            A.cap = 0;
-            const size_t cap = std::max<size_t>(need + need / 2, 1 << 20);
-            ok = hip_ok(h, hipMalloc((void **)&A.dev, cap), "hipMalloc(arena)") &&
-                 hip_ok(h, hipHostMalloc((void **)&A.host, cap, hipHostMallocDefault), "hipHostMalloc(arena)");
-            if (!ok) return nullptr;
-            A.cap = cap;
-        }
-        A.used = 0;
-        b->arena = &A;
-    }
-    auto dalloc = [&](size_t bytes, void **mirror) -> void * {
-        if (mirror) *mirror = nullptr;
-        if (!ok || dry) return nullptr;
-        if (b->arena && align_up(b->arena->used, 256) + bytes <= b->arena->cap) {
-            const size_t off = align_up(b->arena->used, 256);
-            b->arena->used = off + bytes;
-            if (mirror) *mirror = b->arena->host + off;
-            return b->arena->dev + off;
-        }
-        void *p = nullptr;
-        ok = hip_ok(h, hipMalloc(&p, std::max<size_t>(bytes, 256)), "hipMalloc(batch)");
-        if (ok) b->mallocs.push_back(p);
-        return p;
-    };
-    bool async_pending = false;
-    auto up = [&](void *dst, void *mirror, const void *src, size_t bytes) {
-        if (!ok || !bytes || dry) return;
-        if (mirror) {
-            memcpy(mirror, src, bytes);
-        } else {
-            ok = hip_ok(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->S()), "H2D meta");
-            async_pending = true;
-        }
-    };
-
-    // ---- device metadata --------------------------------------------------------------------
-    void *m_rr, *m_rro, *m_rho, *m_ro, *m_ho, *m_oo;
-    b->d_read_region = (uint32_t *)dalloc((size_t)n_reads * 4, &m_rr);
-    b->d_region_read_off = (uint32_t *)dalloc((size_t)(n_regions + 1) * 4, &m_rro);
-    b->d_region_hap_off = (uint32_t *)dalloc((size_t)(n_regions + 1) * 4, &m_rho);
-    b->d_read_off = (uint32_t *)dalloc((size_t)(n_reads + 1) * 4, &m_ro);
-    b->d_hap_off = (uint32_t *)dalloc((size_t)(n_haps + 1) * 4, &m_ho);
-    b->d_out_off = (uint64_t *)dalloc((size_t)(n_regions + 1) * 8, &m_oo);
-    up(b->d_read_region, m_rr, read_region.data(), (size_t)n_reads * 4);
-    up(b->d_region_read_off, m_rro, region_read_off, (size_t)(n_regions + 1) * 4);
-    up(b->d_region_hap_off, m_rho, region_hap_off, (size_t)(n_regions + 1) * 4);
-    up(b->d_read_off, m_ro, read_off, (size_t)(n_reads + 1) * 4);
-    up(b->d_hap_off, m_ho, hap_off, (size_t)(n_haps + 1) * 4);
-    up(b->d_out_off, m_oo, out_off, (size_t)(n_regions + 1) * 8);
-    if (!b->arena && !dry) {  // persistent batch: own status word (arena mode keeps it next to the results)
-        b->d_status = (uint32_t *)dalloc(256, nullptr);
-        if (ok) ok = hip_ok(h, hipMemsetAsync(b->d_status, 0, 4, h->S()), "memset status");
-        // ... and own scratch for the exact pass, which rides behind the forward kernels of every launch (the caller
-        // owns the stream, so the library cannot look at the status word in between)
-        if (ok && n_reads && !sw.no_rescue) {
-            size_t bytes = 0;
-            rescue_geometry(b->max_h, &b->rescue_blocks, &bytes);
-            ok = hip_ok(h, hipMalloc((void **)&b->rescue_scratch, bytes), "hipMalloc(rescue scratch)");
-            if (ok) b->mallocs.push_back(b->rescue_scratch);
-        }
-    }
-
-    mark();  // 4: arena, metadata
-    // ---- finalise classes -------------------------------------------------------------------
-    uint64_t best_cells = 0;
-    for (auto &kv : by_shape) {
-        ShapeClass c = std::move(kv.second);
-        const uint32_t n_items = (uint32_t)c.reads.size();
-        c.identity = (n_items == n_reads);
-        for (uint32_t i = 0; c.identity && i < n_items; ++i) c.identity = (c.reads[i] == i);
-        if (!c.identity && !c.chain) {
-            void *mirror;
-            c.d_reads = (uint32_t *)dalloc((size_t)n_items * 4, &mirror);
-            up(c.d_reads, mirror, c.reads.data(), (size_t)n_items * 4);
-        }
-        if (c.chain) {
-            for (uint32_t g : c.regions) {
-                const uint32_t r0 = region_read_off[g], r1 = region_read_off[g + 1];
-                const uint32_t gs = (uint32_t)(WAVE / c.L) / (uint32_t)c.streams;  // haplotypes per work item
-                const uint32_t nq = (shape[g].nh + gs - 1) / gs;
-                const uint32_t run = reg_run[g];
-                // the haplotype groups of one run next to each other: they sweep the same read bytes, and items that are
-                // launched together find them in L2 (config 3, 10 000 regions: HBM traffic 2.7 x the algorithmic bytes
-                // with the groups a whole pass apart)
-                // A haplotype count that leaves the last wave of a one-stream class partly empty (5 haplotypes: 4 + 1) gives
-                // the remainder to items of its own with 2 or 4 streams of reads, which fill the wave's slots with the same
-                // haplotypes again (chain_streams): 5 haplotypes 0.63 -> 0.96 of the slots busy, 9: 0.75 -> 0.98.
-                uint32_t nq_main = nq, rest = 0, rest_streams = 1;
-                if (c.streams == 1 && c.L == 16 && !(h->flags & PHMM_FLAG_F32_FIRST) && sw.force_streams == 0 && shape[g].nh > 4 && shape[g].nh % 4 != 0) {
-                    rest = shape[g].nh % 4;
-                    rest_streams = (uint32_t)chain_streams(rest, nullptr);
-                    if (rest_streams > 1) nq_main = shape[g].nh / 4;
-                    else rest = 0;
-                }
-                for (uint32_t r = r0; r < r1; r += run)
-                    for (uint32_t q = 0; q < nq_main; ++q)
-                        c.chain_items.push_back(ChainItem{g, (uint16_t)q, (uint8_t)c.K, (uint8_t)c.streams, r, std::min(r1, r + run)});
-                if (rest) {
-                    const uint32_t gs2 = 4 / rest_streams, q0 = nq_main * 4 / gs2, nq2 = (rest + gs2 - 1) / gs2;
-                    const uint32_t run2 = std::min<uint32_t>(CHAIN_MAX_READS, run * rest_streams);
-                    for (uint32_t r = r0; r < r1; r += run2)
-                        for (uint32_t q = 0; q < nq2; ++q)
-                            c.chain_items.push_back(ChainItem{g, (uint16_t)(q0 + q), (uint8_t)c.K, (uint8_t)rest_streams, r, std::min(r1, r + run2)});
-                }
-            }
-            // (the launch is ordered longest item first below, across all classes: one sort there instead of one per class and
-            // another over the whole -- the planner of a 186-region chunk of the ragged mix spent 1.3 of its 2.6 ms here)
-            c.f32_first = (h->flags & PHMM_FLAG_F32_FIRST) && (c.L == 16 || c.L == 32);
-            {   // the chained classes of one lanes-per-pair value (and one precision) share a launch
-                phmm_batch::ChainGroup *grp = nullptr;
-                for (auto &gq : b->chain_groups)
-                    if (gq.L == c.L && gq.f32 == c.f32_first) grp = &gq;
-                if (!grp) {
-                    b->chain_groups.emplace_back();
-                    grp = &b->chain_groups.back();
-                    grp->L = c.L;
-                    grp->f32 = c.f32_first;
-                }
-                grp->items.insert(grp->items.end(), c.chain_items.begin(), c.chain_items.end());
-            }
-            if (c.f32_first) {  // the f64 per-read kernel runs behind the f32 sweep over the reads it flags
-                if (!c.identity) {
-                    void *mr;
-                    c.d_reads = (uint32_t *)dalloc((size_t)n_items * 4, &mr);
-                    up(c.d_reads, mr, c.reads.data(), (size_t)n_items * 4);
-                }
-                c.lds_rows = (uint32_t)align_up((size_t)c.max_r + 1, 8);
-                c.waves_per_block = 1;
-                c.lds_bytes = (size_t)c.lds_rows * kLdsRowBytes;
-                c.grid = dim3(n_items, 1, 1);  // one wave per read, it walks all haplotype groups
-                c.cnd_select = 0;
-                if (!b->d_redo) b->d_redo = (uint8_t *)dalloc(align_up((size_t)n_reads, 256), nullptr);
-            }
-            const char *f32 = c.f32_first ? "_f32" : "";
-            if (c.streams > 1)
-                snprintf(c.name, sizeof c.name, "phmm_forward_chain%s<%d,%d> x%d streams", f32, c.L, c.K, c.streams);
-            else
-                snprintf(c.name, sizeof c.name, "phmm_forward_chain%s<%d,%d>", f32, c.L, c.K);
-        } else if (c.L) {
-            c.lds_rows = (uint32_t)align_up((size_t)c.max_r + 1, 8);
-            const size_t per_wave = (size_t)c.lds_rows * kLdsRowBytes;
-            // One wave per workgroup: waves are independent (no barrier, private LDS), and a multi-wave block
-            // would hold its LDS until its longest read finishes -- with mixed read lengths that idles SIMDs.
-            c.waves_per_block = 1;
-            c.lds_bytes = per_wave * c.waves_per_block;
-            // Enough reads to fill the chip -> one wave walks all haplotype groups of its read (row
-            // constants staged once); otherwise spread the groups over gridDim.y.
-            bool split = (uint64_t)n_items < 4ull * kNumSimd;
-            c.grid = dim3((n_items + c.waves_per_block - 1) / c.waves_per_block, split ? c.max_quads : 1, 1);
-            // a wave alone on its SIMD is latency-bound: the v_cndmask select (one more VALU op, no EXEC round
-            // trip) is ~8 % faster there; with two resident waves the EXEC-masked select wins
-            const uint64_t waves = (uint64_t)n_items * (split ? c.max_quads : 1);
-            c.cnd_select = waves < 2ull * kNumSimd ? 1u : 0u;
-            snprintf(c.name, sizeof c.name, "phmm_forward<%d,%d>", c.L, c.K);
-        } else {
-            // generic: exclusive prefix of pairs per read, scratch for a bounded grid
-            uint64_t acc = 0;
-            for (auto &v : c.pair_first) {
-                const uint64_t nh = v;
-                v = acc;
-                acc += nh;
-            }
-            c.pair_first.push_back(acc);
-            const uint64_t per_thread = 6ull * (c.max_h + 1) * sizeof(double);
-            uint64_t threads = std::min<uint64_t>(align_up(acc, 256), 1024ull * 256);
-            threads = std::min<uint64_t>(threads, std::max<uint64_t>(256, kGenericScratchBytes / per_thread / 256 * 256));
-            c.generic_blocks = (uint32_t)(threads / 256);
-            // scratch can be large: always its own allocation, never the arena
-            if (ok && !dry) ok = hip_ok(h, hipMalloc((void **)&c.d_scratch, threads * per_thread), "hipMalloc(generic scratch)");
-            if (ok && !dry) b->mallocs.push_back(c.d_scratch);
-            void *mirror;
-            c.d_pair_first = (uint64_t *)dalloc(c.pair_first.size() * 8, &mirror);
-            up(c.d_pair_first, mirror, c.pair_first.data(), c.pair_first.size() * 8);
-            snprintf(c.name, sizeof c.name, "phmm_forward_generic");
-        }
-        if (c.cells >= best_cells) {
-            best_cells = c.cells;
-            b->dominant = c.name;
-        }
-        if (sw.trace)
-            fprintf(stderr, "  class %-40s regions %6zu reads %8zu items %8zu cells %.3e max_h %u\n", c.name, c.regions.size(),
-                    c.reads.size(), c.chain_items.size(), (double)c.cells, c.max_h);
-        b->classes.push_back(std::move(c));
-    }
-    mark();  // 5: work items per class
-    {   // What these launches sweep, padding and all (phmm_batch_executed_cells), in lane-cells = steps x 64 lanes x K columns per
-        // wave, and where the padding comes from: columns beyond a haplotype's end (16 K - H), haplotype slots a wave leaves
-        // empty, and steps that carry no read row (the SUM / RESET rows between the reads of a run, the L - 1 steps a run needs to
-        // reach its last lane, the rows the longest of a wave's streams has more than the others).
-        uint64_t swept = 0, pad_cols = 0, pad_slots = 0, t_marks = 0, t_fill = 0, t_uneven = 0, t_uneven_best = 0;  // (t_*: PHMM_TRACE only)
-        auto haps_of = [&](uint32_t g, uint32_t first, uint32_t slots, uint32_t lanes_cols, uint64_t &sum_h, uint32_t &valid) {
-            const uint32_t h0 = region_hap_off[g], nh = region_hap_off[g + 1] - h0;
-            sum_h = 0;
-            valid = 0;
-            for (uint32_t a = first; a < first + slots && a < nh; ++a) {
-                sum_h += std::min<uint32_t>(hap_off[h0 + a + 1] - hap_off[h0 + a], lanes_cols);
-                ++valid;
-            }
-        };
-        for (const auto &grp : b->chain_groups)
-            for (const ChainItem &x : grp.items) {
-                const uint32_t S = std::max<uint32_t>(1, x.streams), L = (uint32_t)grp.L, GS = (64u / L) / S, LK = L * x.k;
-                const uint32_t n = x.read_end - x.read_begin, n_sub = (n + S - 1) / S;
-                uint64_t longest = 0, read_rows = 0;
-                for (uint32_t st = 0; st < S; ++st) {  // (stream st sweeps reads [st n_sub, (st + 1) n_sub) of the run)
-                    const uint32_t lo = std::min(n, st * n_sub), hi = std::min(n, lo + n_sub);
-                    const uint64_t rows = read_off[x.read_begin + hi] - read_off[x.read_begin + lo];
-                    read_rows += rows;
-                    longest = std::max<uint64_t>(longest, rows + 2ull * (hi - lo));
-                }
-                const uint64_t steps = (longest + L) & ~1ull;
-                swept += steps * 64ull * x.k;
-                t_marks += 2ull * n * GS * LK;                                          // the SUM / RESET rows of its reads
-                t_fill += (steps - longest) * 64ull * x.k;                              // reaching the last lane
-                t_uneven += (longest * S - read_rows - 2ull * n) * (uint64_t)GS * LK;   // streams shorter than the longest
-                if (sw.trace && S > 1) {  // ... and what the best cut of the run into S contiguous parts would leave of that
-                    uint64_t lo_b = 0, hi_b = read_rows + 2ull * n;
-                    for (uint32_t i = 0; i < n; ++i) lo_b = std::max<uint64_t>(lo_b, read_off[x.read_begin + i + 1] - read_off[x.read_begin + i] + 2);
-                    while (lo_b < hi_b) {
-                        const uint64_t mid = (lo_b + hi_b) / 2;
-                        uint32_t parts = 1;
-                        uint64_t acc = 0;
-                        for (uint32_t i = 0; i < n; ++i) {
-                            const uint64_t len = read_off[x.read_begin + i + 1] - read_off[x.read_begin + i] + 2;
-                            if (acc + len > mid) {
-                                ++parts;
-                                acc = 0;
-                            }
-                            acc += len;
-                        }
-                        if (parts <= S) hi_b = mid; else lo_b = mid + 1;
-                    }
-                    t_uneven_best += (lo_b * S - read_rows - 2ull * n) * (uint64_t)GS * LK;
-                }
-                uint64_t sum_h;
-                uint32_t valid;
-                haps_of(x.region, (uint32_t)x.quad * GS, GS, LK, sum_h, valid);
-                pad_cols += read_rows * ((uint64_t)valid * LK - sum_h);
-                pad_slots += read_rows * (uint64_t)(GS - valid) * LK;
-            }
-        for (const auto &c : b->classes) {
-            if (c.chain) continue;  // (counted above; the f64 redo behind an f32 sweep touches the reads it flags only)
-            if (!c.L) {
-                swept += c.cells;
-                continue;
-            }
-            const size_t n = c.identity ? n_reads : c.reads.size();
-            const uint32_t per_wave = 64u / (uint32_t)c.L, LK = (uint32_t)(c.L * c.K);
-            for (size_t i = 0; i < n; ++i) {
-                const uint32_t r = c.identity ? (uint32_t)i : c.reads[i], g = read_region[r];
-                const uint32_t quads = (shape[g].nh + per_wave - 1) / per_wave;
-                const uint64_t rows = read_off[r + 1] - read_off[r];
-                swept += (rows + (uint64_t)c.L - 1) * quads * 64ull * (uint64_t)c.K;
-                for (uint32_t qd = 0; qd < quads; ++qd) {
-                    uint64_t sum_h;
-                    uint32_t valid;
-                    haps_of(g, qd * per_wave, per_wave, LK, sum_h, valid);
-                    pad_cols += rows * ((uint64_t)valid * LK - sum_h);
-                    pad_slots += rows * (uint64_t)(per_wave - valid) * LK;
-                }
-            }
-        }
-        if (sw.trace)
-            fprintf(stderr, "phmm plan: swept %.4e lane-cells for %.4e cells: columns %.4e, slots %.4e; chained items' SUM / RESET rows %.4e, fill %.4e, uneven streams %.4e (cut by rows: %.4e)\n",
-                    (double)swept, (double)b->cells, (double)pad_cols, (double)pad_slots, (double)t_marks, (double)t_fill, (double)t_uneven, (double)t_uneven_best);
-        b->swept_cells = swept;
-        b->pad_column_cells = pad_cols;
-        b->pad_slot_cells = pad_slots;
-    }
-    for (auto &grp : b->chain_groups) {
-        // longest item first across all classes of the launch: (rows of the run + its SUM / RESET rows) x the cost of a
-        // step at the item's K (7 VALU per column + ~11 per step)
-        auto cost = [&](const ChainItem &x) {
-            return (uint64_t)(read_off[x.read_end] - read_off[x.read_begin] + 2 * (x.read_end - x.read_begin) + grp.L) *
-                   (uint64_t)(7 * x.k + 11);
-        };
-        {   // (keys made once -- the comparator used to fetch four offsets per comparison -- and unique, so a plain sort keeps
-            // items of equal cost in the order they were made: the groups of a run stay next to each other)
-            const size_t n = grp.items.size();
-            std::vector<uint64_t> cst(n);
-            uint64_t top = 0;
-            for (size_t i = 0; i < n; ++i) top = std::max(top, cst[i] = cost(grp.items[i]));
-            std::vector<uint32_t> idx(n), tmp(n);
-            for (size_t i = 0; i < n; ++i) idx[i] = (uint32_t)i;
-            if (top < (1ull << 33)) {  // LSD radix sort, descending, 11 bits a pass (stable): tens of microseconds for 10^4 items
-                for (int shift = 0; (top >> shift) != 0; shift += 11) {
-                    uint32_t count[2049] = {0};
-                    for (size_t i = 0; i < n; ++i) count[2047 - ((cst[idx[i]] >> shift) & 2047) + 1] += 1;
-                    for (int d = 0; d < 2048; ++d) count[d + 1] += count[d];
-                    for (size_t i = 0; i < n; ++i) tmp[count[2047 - ((cst[idx[i]] >> shift) & 2047)]++] = idx[i];
-                    idx.swap(tmp);
-                }
-            } else {
-                std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return cst[x] > cst[y]; });
-            }
-            std::vector<ChainItem> sorted(n);
-            for (size_t i = 0; i < n; ++i) sorted[i] = grp.items[idx[i]];
-            grp.items.swap(sorted);
-        }
-        // XCD-aware placement.  The haplotype groups of one run (same region, same reads: equal cost, so the stable sort
-        // left them next to each other) sweep the same read bytes.  Workgroups are dealt to the eight XCDs round robin,
-        // each XCD with an L2 of its own, so neighbours in the launch never share one: take eight runs at a time and
-        // emit their first groups, then their second groups, ... -- the groups of a run are then 8 blocks apart, on
-        // the same XCD, started together.
-        {
-            std::vector<ChainItem> out;
-            out.reserve(grp.items.size());
-            auto same_run = [](const ChainItem &x, const ChainItem &y) {
-                return x.region == y.region && x.read_begin == y.read_begin && x.read_end == y.read_end;
-            };
-            size_t i = 0;
-            const size_t n = grp.items.size();
-            while (i < n) {
-                size_t start[9], len[8];  // up to eight consecutive runs
-                int nr = 0;
-                size_t j = i;
-                while (nr < 8 && j < n) {
-                    size_t e = j + 1;
-                    while (e < n && same_run(grp.items[j], grp.items[e])) ++e;
-                    start[nr] = j;
-                    len[nr] = e - j;
-                    ++nr;
-                    j = e;
-                }
-                size_t longest = 0;
-                for (int r = 0; r < nr; ++r) longest = std::max(longest, len[r]);
-                for (size_t q = 0; q < longest; ++q)
-                    for (int r = 0; r < nr; ++r)
-                        if (q < len[r]) out.push_back(grp.items[start[r] + q]);
-                i = j;
-            }
-            grp.items.swap(out);
-        }
-        grp.single_k = grp.items.empty() ? 0 : grp.items[0].k;
-        for (const ChainItem &it : grp.items)
-            if (it.k != grp.single_k) {
-                grp.single_k = 0;
-                break;
-            }
-    }
-    {   // A mixed f64 group goes out as one launch per RANGE of K (the kernel of a range holds only its bodies: no spilled
-        // scalar registers, no scratch); the launches of a batch run side by side on parallel streams (phmm_batch_launch).
-        std::vector<phmm_batch::ChainGroup> split;
-        for (auto &grp : b->chain_groups) {
-            if (grp.f32 || grp.single_k != 0 || grp.items.empty()) {
-                split.push_back(std::move(grp));
-                continue;
-            }
-            phmm_batch::ChainGroup part[kChainRanges];
-            for (const ChainItem &it : grp.items) part[chain_range_of(it.k)].items.push_back(it);  // (order kept: longest first)
-            for (int r = 0; r < kChainRanges; ++r) {
-                if (part[r].items.empty()) continue;
-                part[r].L = grp.L;
-                part[r].f32 = false;
-                part[r].single_k = part[r].items[0].k;
-                for (const ChainItem &it : part[r].items)
-                    if (it.k != part[r].single_k) {
-                        part[r].single_k = -(r + 1);
-                        break;
-                    }
-                split.push_back(std::move(part[r]));
-            }
-        }
-        // the heaviest launch first (it starts on the caller's stream, the others join it from the side streams)
-        auto weight = [&](const phmm_batch::ChainGroup &g) {
-            uint64_t w = 0;
-            for (const ChainItem &x : g.items) w += (uint64_t)(read_off[x.read_end] - read_off[x.read_begin]) * (uint64_t)(7 * x.k + 11);
-            return w;
-        };
-        std::stable_sort(split.begin(), split.end(), [&](const phmm_batch::ChainGroup &x, const phmm_batch::ChainGroup &y) { return weight(x) > weight(y); });
-        b->chain_groups.swap(split);
-    }
-    // the dominant class under the name of the kernel that runs it (what rocprofv3 reports): the body alone for a launch
-    // whose items share one K, the kernel of its range of K otherwise
-    for (const auto &c : b->classes) {
-        if (!c.chain || b->dominant != c.name) continue;
-        for (const auto &grp : b->chain_groups) {
-            if (grp.L != c.L || grp.f32 != c.f32_first) continue;
-            char nm[64] = {0};
-            if (grp.f32) {
-                if (grp.single_k == c.K) snprintf(nm, sizeof nm, "phmm_forward_chain_f32<%d,%d>", c.L, c.K);
-                else if (grp.single_k == 0) snprintf(nm, sizeof nm, "phmm_forward_chain_f32_any<%d> (K = %d)", c.L, c.K);
-            } else if (grp.single_k == c.K) {
-                snprintf(nm, sizeof nm, "phmm_forward_chain_k<%d,%d>", c.L, c.K);
-            } else if (grp.single_k < 0 && chain_range_of(c.K) == -grp.single_k - 1) {
-#define PHMM_RANGE(R, LO, HI) \
-    if (R == -grp.single_k - 1) snprintf(nm, sizeof nm, "phmm_forward_chain<%d,%d,%d> (K = %d)", c.L, LO, HI, c.K);
-                PHMM_CHAIN_RANGES(PHMM_RANGE)
-#undef PHMM_RANGE
-            }
-            if (nm[0]) {
-                b->dominant = nm;
-                if (c.streams > 1) b->dominant += " x" + std::to_string(c.streams) + " streams";
-                break;
-            }
-        }
-        break;
-    }
-    mark();  // 6: sorting, placement, ranges
-    if (sw.trace)
-        fprintf(stderr, "  plan phases (us): shapes %.0f, <L,K> %.0f, classes %.0f, metadata %.0f, items %.0f, order %.0f\n", marks[1] - marks[0],
-                marks[2] - marks[1], marks[3] - marks[2], marks[4] - marks[3], marks[5] - marks[4], marks[6] - marks[5]);
-    for (auto &grp : b->chain_groups) {
-        void *mirror;
-        grp.d_items = (ChainItem *)dalloc(grp.items.size() * sizeof(ChainItem), &mirror);
-        up(grp.d_items, mirror, grp.items.data(), grp.items.size() * sizeof(ChainItem));
-    }
-    // host staging vectors die at return: finish the async copies first (arena mode copied into the mirror)
-    if (ok && async_pending) ok = hip_ok(h, hipStreamSynchronize(h->S()), "sync(meta)");
-    if (!ok) return nullptr;
+    const BatchOffsets o{n_regions, region_read_off, region_hap_off, read_off, hap_off, out_off};
+    b->plan = plan_batch(o, h->sw, h->flags, h->gpu_sharers);
+    if (!place_batch(h, b, o, use_arena, extra_arena_bytes)) return nullptr;
     return owner.release();
 }
 
@@ -1228,7 +601,7 @@ phmm_batch *phmm_batch_create(phmm_handle *h, uint32_t n_regions, const uint32_t
 // What the planned launches sweep, in lane-cells: every row of every wave x 64 lanes x its K columns -- the columns beyond a
 // haplotype's end inside its 16 x K lanes, haplotype slots a wave leaves empty, the rows of a multi-stream item's shorter
 // streams.  executed / cells is the padding a batch's shapes cost (1.01 for the uniform config-2 batch: 304 columns for 300).
-uint64_t phmm_batch_executed_cells(const phmm_batch *b) { return b ? b->swept_cells : 0; }
+uint64_t phmm_batch_executed_cells(const phmm_batch *b) { return b ? b->plan.swept_cells : 0; }
 
 int phmm_batch_bind_device(phmm_batch *b, const uint8_t *d_read_bases, const uint8_t *d_base_q, const uint8_t *d_ins_q,
                            const uint8_t *d_del_q, const uint8_t *d_gcp, const uint8_t *d_hap_bases, double *d_out) {
@@ -1309,9 +682,9 @@ static ForwardParams base_params(const phmm_batch *b) {
 static int launch_rescue_pass(phmm_batch *b, double *scratch, uint32_t n_blocks, bool force, hipStream_t stream) {
     RescueParams rp{};
     rp.f = base_params(b);
-    rp.n_reads = b->n_reads;
+    rp.n_reads = b->plan.n_reads;
     rp.scratch = scratch;
-    rp.max_h = b->max_h;
+    rp.max_h = b->plan.max_h;
     rp.n_blocks = n_blocks;
     rp.force = force ? 1u : 0u;
     return hip_ok(b->h, launch_rescue(rp, stream), "phmm_rescue") ? PHMM_OK : PHMM_ERR_HIP;
@@ -1340,11 +713,11 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
     }
     DeviceGuard dg(h->device);
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : b->home_stream;
-    if (b->d_redo && !hip_ok(h, hipMemsetAsync(b->d_redo, 0, b->n_reads, stream), "memset redo")) return PHMM_ERR_HIP;
+    if (b->d_redo && !hip_ok(h, hipMemsetAsync(b->d_redo, 0, b->plan.n_reads, stream), "memset redo")) return PHMM_ERR_HIP;
     // The chained sweeps: one launch per lanes-per-pair value, precision and (mixed batches) range of K.  Several launches
     // run side by side: the first on the caller's stream, the others on the handle's side streams between a fork and a
     // join event -- each alone would leave the chip to its own tail before the next could start.
-    const size_t n_groups = b->chain_groups.size();
+    const size_t n_groups = b->plan.chain_groups.size();
     // (not while the chunks of a pipelined host call are in flight: those already overlap each other on the slot streams,
     // and forks of several chunks would queue behind one another on the side streams -- 1 536 mixed regions through host
     // buffers: 25 ms without, 32 ms with)
@@ -1359,9 +732,11 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
         if (!h->ev_fork && !hip_ok(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming), "hipEventCreate")) return PHMM_ERR_HIP;
         if (!hip_ok(h, hipEventRecord(h->ev_fork, stream), "hipEventRecord")) return PHMM_ERR_HIP;
     }
-    auto launch_class = [&](ShapeClass &c) -> int {
+    auto launch_class = [&](size_t ci) -> int {
+        const ShapeClass &c = b->plan.classes[ci];
+        const phmm_batch::ClassDevice &cd = b->class_dev[ci];
         ForwardParams p = base_params(b);
-        p.class_reads = c.identity ? nullptr : c.d_reads;
+        p.class_reads = c.identity ? nullptr : cd.reads;
         p.n_items = (uint32_t)c.reads.size();
         p.lds_rows = c.lds_rows;
         p.cnd_select = c.cnd_select;
@@ -1376,9 +751,9 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
         } else {
             GenericParams gp{};
             gp.f = p;
-            gp.scratch = c.d_scratch;
+            gp.scratch = cd.scratch;
             gp.max_h = c.max_h;
-            gp.pair_first = c.d_pair_first;
+            gp.pair_first = cd.pair_first;
             gp.n_pairs = c.pair_first.back();
             gp.n_blocks = c.generic_blocks;
             e = gp.n_pairs ? launch_generic(gp, stream) : hipSuccess;
@@ -1391,8 +766,8 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
     // (The mixed batch resident, three runs each on one box: 15.59-15.66 ms against 15.80-15.89 the other way round.)
     const bool early_classes = fork;
     if (early_classes)
-        for (auto &c : b->classes)
-            if (!c.chain && launch_class(c) != PHMM_OK) return PHMM_ERR_HIP;
+        for (size_t ci = 0; ci < b->plan.classes.size(); ++ci)
+            if (!b->plan.classes[ci].chain && launch_class(ci) != PHMM_OK) return PHMM_ERR_HIP;
     bool side_used[phmm_handle::kSideStreams] = {};
     // (Measured and dropped, round 5: dealing the launches to the streams by load, every stream sending its lightest first -- in the
     // mixed batch's timeline the two lightest launches trail the second and third heaviest -- : 15.56-15.67 ms either way.)
@@ -1404,11 +779,11 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
             if (!side_used[si] && !hip_ok(h, hipStreamWaitEvent(s_x, h->ev_fork, 0), "hipStreamWaitEvent")) return PHMM_ERR_HIP;
             side_used[si] = true;
         }
-        auto &grp = b->chain_groups[gi];
+        const ChainGroup &grp = b->plan.chain_groups[gi];
         if (grp.items.empty()) continue;
         ChainParams cp{};
         cp.f = base_params(b);
-        cp.items = grp.d_items;
+        cp.items = b->d_group_items[gi];
         cp.n_items = (uint32_t)grp.items.size();
         cp.redo = grp.f32 ? b->d_redo : nullptr;
         hipStream_t s = s_x;
@@ -1420,12 +795,12 @@ int phmm_batch_launch(phmm_batch *b, void *stream_v) {
                              !hip_ok(h, hipStreamWaitEvent(stream, h->ev_join[i], 0), "hipStreamWaitEvent")))
             return PHMM_ERR_HIP;
     // (the per-read classes that depend on no chained launch went out in front of the fork, above)
-    for (auto &c : b->classes)
-        if (!(early_classes && !c.chain) && launch_class(c) != PHMM_OK) return PHMM_ERR_HIP;
+    for (size_t ci = 0; ci < b->plan.classes.size(); ++ci)
+        if (!(early_classes && !b->plan.classes[ci].chain) && launch_class(ci) != PHMM_OK) return PHMM_ERR_HIP;
     // Results below kRescueBelow are redone in the reference's operation order.  Persistent batches and the
     // engine-level call carry the pass in-stream (it returns at once unless a forward kernel asked for it); the
     // host-buffer path looks at the status word in finish_compute instead and pays nothing in the common case.
-    if (b->rescue_scratch && !h->sw.no_rescue && b->n_reads)
+    if (b->rescue_scratch && !h->sw.no_rescue && b->plan.n_reads)
         return launch_rescue_pass(b, b->rescue_scratch, b->rescue_blocks, false, stream);
     return PHMM_OK;
 }
@@ -1773,7 +1148,7 @@ int finish_compute(phmm_handle *h, PendingCompute *p) {
             // some pair came out below kRescueBelow: redo those in the reference's operation order, fetch again
             uint32_t nb = 0;
             h->stat_rescue_passes += 1;
-            if (!ensure_arena_rescue(h, A, b->max_h, &nb) || launch_rescue_pass(b, A.rescue, nb, true, S) != PHMM_OK ||
+            if (!ensure_arena_rescue(h, A, b->plan.max_h, &nb) || launch_rescue_pass(b, A.rescue, nb, true, S) != PHMM_OK ||
                 !hip_ok(h, hipStreamSynchronize(S), "sync(rescue)") || (!p->zero_copy && !fetch())) {
                 st = PHMM_ERR_HIP;
             } else {
@@ -1827,10 +1202,10 @@ phmm_batch *batch_create_in_arena(phmm_handle *h, uint32_t n_regions, const uint
 }
 BatchView batch_view(const phmm_batch *b) {
     BatchView v{};
-    v.n_regions = b->n_regions;
-    v.n_reads = b->n_reads;
-    v.n_haps = b->n_haps;
-    v.max_h = b->max_h;
+    v.n_regions = b->plan.n_regions;
+    v.n_reads = b->plan.n_reads;
+    v.n_haps = b->plan.n_haps;
+    v.max_h = b->plan.max_h;
     v.n_out = b->n_out;
     v.read_bytes = b->read_bytes;
     v.hap_bytes = b->hap_bytes;
@@ -1845,8 +1220,8 @@ BatchView batch_view(const phmm_batch *b) {
 }
 void batch_set_status(phmm_batch *b, uint32_t *d_status) { b->d_status = d_status; }
 bool batch_set_inline_rescue(phmm_handle *h, phmm_batch *b) {
-    if (!b->n_reads || h->sw.no_rescue) return true;
-    if (!ensure_arena_rescue(h, *b->arena, b->max_h, &b->rescue_blocks)) return false;
+    if (!b->plan.n_reads || h->sw.no_rescue) return true;
+    if (!ensure_arena_rescue(h, *b->arena, b->plan.max_h, &b->rescue_blocks)) return false;
     b->rescue_scratch = b->arena->rescue;
     return true;
 }
@@ -2185,7 +1560,7 @@ int engine_enqueue(phmm_handle *h, const phmm_engine_config *cfg, uint32_t n_reg
         // the post-step consumes the likelihoods on the device, so the exact pass below kRescueBelow rides in-stream
         // between the forward kernels and the post-step (phmm_batch_launch); nothing of this slot is in flight now
         if (ok && n_reads && !h->sw.no_rescue) {
-            ok = ensure_arena_rescue(h, A, b->max_h, &b->rescue_blocks);
+            ok = ensure_arena_rescue(h, A, b->plan.max_h, &b->rescue_blocks);
             if (ok) b->rescue_scratch = A.rescue;
         }
         uint32_t max_r = 0;
@@ -2458,29 +1833,26 @@ int phmm_plan_describe(unsigned flags, uint32_t concurrent_callers, uint32_t n_r
         if (region_read_off && region_hap_off)
             for (uint32_t g = 0; g < n_regions; ++g)
                 oo[g + 1] = oo[g] + (uint64_t)(region_read_off[g + 1] - region_read_off[g]) * (region_hap_off[g + 1] - region_hap_off[g]);
-        phmm_handle h;  // host-only: carries the flags and the planner's switches (this process's PHMM_* environment), never a device
-        read_env_switches(h.sw);
-        h.flags = flags;
-        h.gpu_sharers = concurrent_callers ? concurrent_callers : 1u;
-        // (a dry batch owns nothing on a device: plain delete, also when something below throws)
-        std::unique_ptr<phmm_batch> owner(batch_create_impl(&h, n_regions, region_read_off, region_hap_off, read_off, hap_off, oo.data(), false, 0, true));
-        phmm_batch *b = owner.get();
-        if (!b) return h.err_code == PHMM_ERR_NO_MEMORY ? PHMM_ERR_NO_MEMORY : PHMM_ERR_INVALID_ARG;
-        info->cells = b->cells;
-        info->n_launches = phmm_batch_num_launches(b);
-        for (const auto &g : b->chain_groups) {
+        if (validate_offsets(n_regions, region_read_off, region_hap_off, read_off, hap_off, oo.data(), nullptr)) return PHMM_ERR_INVALID_ARG;
+        Switches sw;  // the planner's switches: this process's PHMM_* environment
+        read_env_switches(sw);
+        const BatchPlan plan = plan_batch(BatchOffsets{n_regions, region_read_off, region_hap_off, read_off, hap_off, oo.data()}, sw, flags,
+                                          concurrent_callers ? concurrent_callers : 1u);
+        info->cells = plan.cells;
+        info->n_launches = num_launches(plan);
+        for (const auto &g : plan.chain_groups) {
             info->n_chain_launches += 1;
             info->chain_items += g.items.size();
             uint32_t fewest = 0xffffffffu;
             for (const ChainItem &it : g.items) fewest = std::min(fewest, it.read_end - it.read_begin);
             info->min_reads_per_run = info->min_reads_per_run ? std::min(info->min_reads_per_run, fewest) : fewest;
         }
-        for (const auto &c : b->classes)
+        for (const auto &c : plan.classes)
             if (c.chain) info->chain_cells += c.cells;
-        info->swept_cells = b->swept_cells;
-        info->pad_column_cells = b->pad_column_cells;
-        info->pad_slot_cells = b->pad_slot_cells;
-        snprintf(info->dominant_kernel, sizeof info->dominant_kernel, "%s", b->dominant.c_str());
+        info->swept_cells = plan.swept_cells;
+        info->pad_column_cells = plan.pad_column_cells;
+        info->pad_slot_cells = plan.pad_slot_cells;
+        snprintf(info->dominant_kernel, sizeof info->dominant_kernel, "%s", plan.dominant.c_str());
         return PHMM_OK;
     } catch (const std::bad_alloc &) {
         return PHMM_ERR_NO_MEMORY;
@@ -2489,16 +1861,11 @@ int phmm_plan_describe(unsigned flags, uint32_t concurrent_callers, uint32_t n_r
     }
 }
 
-uint64_t phmm_batch_cells(const phmm_batch *b) { return b ? b->cells : 0; }
-uint64_t phmm_batch_algorithmic_bytes(const phmm_batch *b) { return b ? b->alg_bytes : 0; }
+uint64_t phmm_batch_cells(const phmm_batch *b) { return b ? b->plan.cells : 0; }
+uint64_t phmm_batch_algorithmic_bytes(const phmm_batch *b) { return b ? b->plan.alg_bytes : 0; }
 uint32_t phmm_batch_num_launches(const phmm_batch *b) {
-    if (!b) return 0;
-    uint32_t n = 0;
-    for (const auto &g : b->chain_groups) n += g.items.empty() ? 0u : 1u;
-    for (const auto &c : b->classes)
-        if (!c.chain || c.f32_first) n += 1u;  // per-read classes, and the f64 redo behind an f32 sweep
-    return n;
+    return b ? num_launches(b->plan) : 0;
 }
-const char *phmm_batch_dominant_kernel(const phmm_batch *b) { return b ? b->dominant.c_str() : ""; }
+const char *phmm_batch_dominant_kernel(const phmm_batch *b) { return b ? b->plan.dominant.c_str() : ""; }
 
 }  // extern "C"

@@ -40,7 +40,7 @@ def _makefile_values(flag):
 
 def test_the_sweep_covers_exactly_the_compiled_instances():
     per_read, chain, chain32 = _source("phmm_kernels.hip"), _source("phmm_chain_kernels.hip"), _source("phmm_chain32_kernels.hip")
-    internal, device, api = _source("phmm_internal.hpp"), _source("phmm_device.hpp"), _source("phmm_api.cpp")
+    internal, device, api = _source("phmm_internal.hpp"), _source("phmm_device.hpp"), _source("phmm_plan.hpp") + _source("phmm_plan.cpp")
     # per read: the launch table and the planner's list name the same K, once each, for every compiled lane count
     k_list = tuple(int(k) for k in re.findall(r"X\(L,\s*(\d+)\)", _macro_body(per_read, "PHMM_K_LIST")))
     m = re.search(r"const\s+int\s+kInstantiatedK\[\]\s*=\s*\{([^}]*)\}", per_read)

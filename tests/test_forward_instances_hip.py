@@ -39,7 +39,7 @@ CHAIN32_K = tuple(range(2, 26))          # PHMM_CHAIN32_K_LIST
 CHAIN32_LANES = (16, 32)                 # -DPHMM_CHAIN32_L
 CHAIN_RANGES = ((2, 9), (10, 15), (16, 19), (20, 25))   # PHMM_CHAIN_RANGES
 SDWA_MIN_K, CND_MAX_K, TWO_WAVE_MAX_K = 21, 13, 25      # phmm_device.hpp
-NUM_SIMD = 1024                          # phmm_api.cpp, kNumSimd
+NUM_SIMD = 1024                          # phmm_plan.hpp, kNumSimd
 CHAIN_MAX_READS = 64
 RUN = 5                                  # forced run length: divides none of the read counts below
 
