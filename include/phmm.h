@@ -886,6 +886,97 @@ int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
                          uint32_t *hap_event_type);
 
 /*
+ * The activity profile: what the reference computes in front of assembly to decide which stretches of a contig become assembly
+ * regions (src/haplotype/haplotype_caller_engine.rs:627-752 update_activity_profile / update_ref_vs_any_results, :754-899
+ * parse_record, :908-1107 calculate_activity_probabilities, :1464-1749 alignment_context_creation and what it calls), for many
+ * windows, samples and reads in ONE call.  Four stages, all on the device:
+ *   1. pileup      one wave per read restates parse_record: a slot per base of an M / = / X element, per base of a D element and
+ *                  per I element (ONE entry at the current position; its base is the first inserted base, compared with the
+ *                  reference base there), in CIGAR order.  A slot holds counted (quality >= min_base_quality, or a deletion),
+ *                  is_alt (:1558-1590, evaluated for counted entries only, so an uncounted base adds no soft clips either), the
+ *                  quality (30 for a deletion, :111) and "adds the read's count_high_quality_soft_clips" (qualities > 28, :117).
+ *                  Kept as written: next_to_soft_clip_or_indel (:1596-1652) loop for loop; an I element before the window's start
+ *                  skips `cig_index += 1`, and the lagging index picks the three CIGAR elements a later deletion inspects
+ *                  (:1536-1547); an I element at or past the bounds' end ends the read, a D / M element only itself
+ *   2. sums        one lane per position walks the samples in order, a sample's reads in order and a read's slots in CIGAR order:
+ *                  genotype_likelihoods[i] += term[is_alt][quality][i] (update_heterozygous_likelihood :1724-1749; the addends
+ *                  are host-made with the reference's operations, the middle ones through approximate_log10_sum_log10,
+ *                  src/utils/math_utils.rs:314-332), read_counts / ref_depth / non_ref_depth, the soft-clip RunningAverage shared
+ *                  by all samples (math_utils.rs:434-477: mean += (obs - mean) / n), gl[i] -= read_counts * log10(ploidy),
+ *                  and the PLs of Genotype::build (src/genotype/genotype_builder.rs:104-117, gls_to_pls)
+ *   3. is-active   phmm_allele_frequency's kernel on those PLs with one event per position: the reference allele and one
+ *                  symbolic alternate of length 0 (the indel prior class), ploidy + 1 genotypes.  is_active_prob =
+ *                  CALLED ? (1 - 10^((qual as u8) / -10)) as f32 : 0  (:1080-1085, src/utils/quality_utils.rs:82-104; `as u8`
+ *                  saturates, NaN gives 0)
+ *   4. band-pass   BandPassActivityProfile::add (src/activity_profile/band_pass_activity_profile.rs:36-105, :210-280;
+ *                  src/activity_profile/activity_profile.rs:231-341; activity_profile_state.rs) as a gather.  The Gaussian kernel
+ *                  is host-made (make_kernel, determine_filter_size with MIN_PROB_TO_KEEP_IN_FILTER 1e-5, math_utils.rs:383-415)
+ *                  and cast to f32 tap by tap; F is the filter size in use.  A state whose (soft-clip mean as f32) >= 6.0 (:75)
+ *                  becomes mult = #{i in [-K, K] : 0 <= s + i <= contig length} states, K = min(mean as f32,
+ *                  max_prob_propagation as f32) as i64, and as written every one of them re-emits the whole band around the ADDED
+ *                  position; any other state has mult = 1.  List entry q = the f32 sum over the sources s ascending, |q - s| <= F,
+ *                  prob_s > 0, of prob_s * tap[q - s + F] added mult_s times in a row.  Positions before the profile's first
+ *                  state and past the contig length are dropped (the contig length itself is kept, as the reference tests `>`).
+ *                  The list is as long as the furthest of: s + 1 for a state without probability, min(s + F, contig length) + 1
+ *                  for one with (both from the profile's start)
+ * EQUAL to a statement-by-statement restatement: the integers, gl, the soft-clip mean and the band-passed values bit for bit;
+ * qual within phmm_allele_frequency's bound with equal flags; is_active_prob is the table value of the device's own
+ * `qual as u8`.  Results are identical from run to run and whatever the batch.
+ * Per call: ploidy 1..=PHMM_ACTIVITY_MAX_PLOIDY; min_base_quality; the pseudo counts and stand_min_conf of
+ * phmm_allele_frequency (the SNP count is part of the contract but no allele here is of its class); max_prob_propagation;
+ * max_filter_size (the reference: 50, at most PHMM_ACTIVITY_MAX_FILTER), sigma (17.0), adaptive_filter_size (1); profile_size =
+ * the reference's inner_chunk_size: every run of profile_size positions of a window is a BandPassActivityProfile of its own,
+ * 0 = one per window.
+ * Per window w (the reference's outer chunk): window_start (outer_chunk_location.start), window_len (its size), the contig's
+ * length (target_len; the window must end inside it), window_ref_off [n_windows+1] / ref_bases: the reference bases from
+ * window_start on, at least window_len of them.
+ * Per (window, sample) group g = w * n_samples + s: group_read_off [n_windows * n_samples + 1], its reads after the caller's
+ * read_is_filtered IN THE ORDER THE BAM FETCH RETURNED THEM (every sum runs in it); read_pos (0-based) must not decrease
+ * inside a group.  Per read: read_cigar_off [n_reads+1] / read_cigar (BAM-encoded), read_off [n_reads+1] / read_bases (ASCII) /
+ * read_quals.
+ * Outputs; every pointer except window_status may be NULL and is then neither copied back nor written.  With P = the
+ * positions of all windows in order (position p of window w at pos_w + p, pos_w = the lengths of the windows before it):
+ *   window_status [n_windows]    0, or negative where the reference panics: PHMM_ACT_STATUS_REF_SKIP an N element in a CIGAR of
+ *                  the window, PHMM_ACT_STATUS_CIGAR_OVERRUN a CIGAR that consumes more read bases than its read has (the first
+ *                  such read decides).  Then every output of the window is 0, its lists are empty, other windows are unaffected
+ *   read_counts, ref_depth, non_ref_depth [P * n_samples]   at (pos_w + p) * n_samples + s
+ *   gl, pl [P * n_samples * (ploidy + 1)]                   RefVsAnyResult::genotype_likelihoods and the PLs built from them
+ *   soft_clip_mean (f64), soft_clip_count, qual, af_flags (PHMM_AF_*), is_active_prob (float) [P]
+ *   filter_size [1]; profile_len [profiles]; profile_prob (float) [P + profiles * max_filter_size]: the profiles of all windows
+ *                  in order (ceil(window_len / profile_size) per window), profile k's list from P_k + k * max_filter_size, P_k
+ *                  the global index of its first position; profile_len[k] entries of it are the state list, the rest is 0
+ * Out of scope, the caller's: BAM reading and read_is_filtered, limiting_interval, pop_ready_assembly_regions and below, the
+ * depth runs for ANI (they read ref_depth + non_ref_depth).
+ * Footprint: staging for the inputs and the wanted outputs; on the device alone, kept by the handle until phmm_destroy, 6 bytes
+ * per pileup slot and about 130 bytes per position plus the outputs not asked for.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): ploidy 0 or above the maximum, no samples,
+ * a required array NULL, offsets that do not start at 0 or are not monotonic, fewer reference bases than the window is long, a
+ * window that ends past its contig, a position from 2^62 on, read_pos negative or smaller than that of the read before it in its
+ * group, a CIGAR element with an operator above 8 or length 0, a sigma the reference's assertions refuse, 2^31 positions.
+ * n_windows == 0, windows of length 0 and groups without reads are fine.  One thread per handle.
+ *
+ * phmm_activity_band_kernel: the host-made kernel alone (filter_size [1], kernel [2 * filter_size + 1] <= 2 * max_filter_size + 1
+ * doubles, NULL to ask for the size only); phmm_activity_term_table: the addends of stage 2, [2][256][ploidy + 1].  Both for
+ * parity tests.
+ */
+#define PHMM_ACTIVITY_MAX_PLOIDY 64u
+#define PHMM_ACTIVITY_MAX_FILTER 65536u
+#define PHMM_ACT_STATUS_REF_SKIP (-1)
+#define PHMM_ACT_STATUS_CIGAR_OVERRUN (-2)
+int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples, uint32_t ploidy, uint32_t min_base_quality,
+                          double ref_pseudo_count, double snp_pseudo_count, double indel_pseudo_count, double stand_min_conf,
+                          uint32_t max_prob_propagation, uint32_t max_filter_size, double sigma, int adaptive_filter_size,
+                          uint32_t profile_size, const uint64_t *window_start, const uint32_t *window_len,
+                          const uint64_t *window_contig_length, const uint32_t *window_ref_off, const uint8_t *ref_bases,
+                          const uint32_t *group_read_off, const int64_t *read_pos, const uint32_t *read_cigar_off,
+                          const uint32_t *read_cigar, const uint32_t *read_off, const uint8_t *read_bases, const uint8_t *read_quals,
+                          int32_t *window_status, uint32_t *read_counts, uint32_t *ref_depth, uint32_t *non_ref_depth, double *gl,
+                          int32_t *pl, double *soft_clip_mean, uint32_t *soft_clip_count, double *qual, uint32_t *af_flags,
+                          void *is_active_prob, uint32_t *filter_size, void *profile_prob, uint32_t *profile_len);
+int phmm_activity_band_kernel(uint32_t max_filter_size, double sigma, int adaptive_filter_size, uint32_t *filter_size, double *kernel);
+int phmm_activity_term_table(uint32_t ploidy, double *term);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):
@@ -924,7 +1015,7 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name);
  * the server to leave the chip first.  tools/server_trace.cpp prints a call's timeline from it. */
 uint32_t phmm_server_trace(int device_id, void *out, uint32_t cap);
 
-/* What the library was built from: "cigar=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
+/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
  * family (tools/source_hash.py) at compile time.  smoke() and bench.py compare it with the tree they run in. */
 const char *phmm_build_info(void);
 

@@ -796,3 +796,143 @@ pub fn calculate_cigars(pairs: &[(&[u8], &[u8])], parameters: (i32, i32, i32, i3
         })
         .collect()
 }
+
+/// One window of `activity_profile`: `outer_chunk_location.start`, the reference bases from there on (the window is as long
+/// as they are), the contig's length, and per sample the reads that passed `read_is_filtered`, in fetch order, as
+/// (pos, BAM-encoded CIGAR, bases in ASCII, qualities).
+pub struct ActivityWindow<'a> {
+    pub start: u64,
+    pub reference: &'a [u8],
+    pub contig_length: u64,
+    pub samples: Vec<Vec<(i64, Vec<u32>, &'a [u8], &'a [u8])>>,
+}
+
+/// What `activity_profile` returns: per window its status (negative: the reference panics there), then over the positions of
+/// all windows in order `depth[position * n_samples + sample]` (ref_depth + non_ref_depth, what the ANI depth runs read), the
+/// soft-clip average and is_active_prob, and per profile (`ceil(window length / profile_size)` per window) its band-passed
+/// state list -- what `pop_ready_assembly_regions` scans.
+pub struct ActivityOutput {
+    pub window_status: Vec<i32>,
+    pub depth: Vec<u32>,
+    pub soft_clip_mean: Vec<f64>,
+    pub is_active_prob: Vec<f32>,
+    pub profiles: Vec<Vec<f32>>,
+}
+
+/// `update_activity_profile` + `calculate_activity_probabilities` up to `BandPassActivityProfile::add`
+/// (src/haplotype/haplotype_caller_engine.rs:627-1107) for a batch of windows.  The pseudo counts and `stand_min_conf` are
+/// those of the `active_region_evaluation_genotyper_engine`; the band-pass runs at the reference's constants.
+pub fn activity_profile(
+    windows: &[ActivityWindow],
+    n_samples: usize,
+    ploidy: usize,
+    bq: u8,
+    pseudo_counts: (f64, f64, f64),
+    stand_min_conf: f64,
+    max_prob_propagation: usize,
+    profile_size: usize,
+) -> ActivityOutput {
+    const MAX_FILTER_SIZE: u32 = 50;
+    const SIGMA: f64 = 17.0;
+    let n = windows.len();
+    let window_start: Vec<u64> = windows.iter().map(|w| w.start).collect();
+    let window_len: Vec<u32> = windows.iter().map(|w| w.reference.len() as u32).collect();
+    let contig_length: Vec<u64> = windows.iter().map(|w| w.contig_length).collect();
+    let (mut ref_off, mut group_off, mut cigar_off, mut read_off): (Vec<u32>, Vec<u32>, Vec<u32>, Vec<u32>) = (vec![0], vec![0], vec![0], vec![0]);
+    let (mut refs, mut bases, mut quals): (Vec<u8>, Vec<u8>, Vec<u8>) = (Vec::new(), Vec::new(), Vec::new());
+    let mut cigars: Vec<u32> = Vec::new();
+    let mut read_pos: Vec<i64> = Vec::new();
+    for w in windows {
+        assert_eq!(w.samples.len(), n_samples, "activity_profile: every window carries every sample");
+        refs.extend_from_slice(w.reference);
+        ref_off.push(refs.len() as u32);
+        for reads in &w.samples {
+            for (pos, cigar, b, q) in reads {
+                read_pos.push(*pos);
+                cigars.extend_from_slice(cigar);
+                cigar_off.push(cigars.len() as u32);
+                bases.extend_from_slice(b);
+                quals.extend_from_slice(q);
+                read_off.push(bases.len() as u32);
+            }
+            group_off.push(read_pos.len() as u32);
+        }
+    }
+    let n_pos: usize = window_len.iter().map(|l| *l as usize).sum();
+    let mut profile_lengths: Vec<usize> = Vec::new();
+    for l in &window_len {
+        let l = *l as usize;
+        let step = if profile_size == 0 { l } else { profile_size };
+        let mut at = 0usize;
+        while at < l {
+            profile_lengths.push(step.min(l - at));
+            at += step;
+        }
+    }
+    let n_profiles = profile_lengths.len();
+    let mut window_status = vec![0i32; n];
+    let (mut ref_depth, mut non_ref_depth) = (vec![0u32; n_pos * n_samples], vec![0u32; n_pos * n_samples]);
+    let mut soft_clip_mean = vec![0f64; n_pos];
+    let mut is_active_prob = vec![0f32; n_pos];
+    let mut profile_prob = vec![0f32; n_pos + n_profiles * MAX_FILTER_SIZE as usize];
+    let mut profile_len = vec![0u32; n_profiles];
+    let mut filter_size = 0u32;
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_activity_profile(
+                h,
+                n as u32,
+                n_samples as u32,
+                ploidy as u32,
+                bq as u32,
+                pseudo_counts.0,
+                pseudo_counts.1,
+                pseudo_counts.2,
+                stand_min_conf,
+                max_prob_propagation as u32,
+                MAX_FILTER_SIZE,
+                SIGMA,
+                1,
+                profile_size as u32,
+                window_start.as_ptr(),
+                window_len.as_ptr(),
+                contig_length.as_ptr(),
+                ref_off.as_ptr(),
+                refs.as_ptr(),
+                group_off.as_ptr(),
+                read_pos.as_ptr(),
+                cigar_off.as_ptr(),
+                cigars.as_ptr(),
+                read_off.as_ptr(),
+                bases.as_ptr(),
+                quals.as_ptr(),
+                window_status.as_mut_ptr(),
+                std::ptr::null_mut(),
+                ref_depth.as_mut_ptr(),
+                non_ref_depth.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                soft_clip_mean.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                is_active_prob.as_mut_ptr() as *mut std::os::raw::c_void,
+                &mut filter_size,
+                profile_prob.as_mut_ptr() as *mut std::os::raw::c_void,
+                profile_len.as_mut_ptr(),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP activity_profile failed ({}): {}", rc, last_error(h));
+        }
+    });
+    let mut profiles = Vec::with_capacity(n_profiles);
+    let mut first = 0usize;
+    for (k, positions) in profile_lengths.iter().enumerate() {
+        let at = first + k * MAX_FILTER_SIZE as usize;
+        profiles.push(profile_prob[at..at + profile_len[k] as usize].to_vec());
+        first += positions;
+    }
+    let depth = ref_depth.iter().zip(non_ref_depth.iter()).map(|(a, b)| a + b).collect();
+    ActivityOutput { window_status, depth, soft_clip_mean, is_active_prob, profiles }
+}

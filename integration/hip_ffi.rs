@@ -108,6 +108,11 @@ pub const PHMM_EV_STATUS_BLOCK: c_int = -2;
 pub const PHMM_EV_STATUS_MERGE: c_int = -3;
 pub const PHMM_EV_STATUS_CIGAR_OVERRUN: c_int = -4;
 pub const PHMM_EV_STATUS_ALLELES: c_int = -5;
+/// `phmm_activity_profile`: limits, window statuses
+pub const PHMM_ACTIVITY_MAX_PLOIDY: c_uint = 64;
+pub const PHMM_ACTIVITY_MAX_FILTER: c_uint = 65536;
+pub const PHMM_ACT_STATUS_REF_SKIP: c_int = -1;
+pub const PHMM_ACT_STATUS_CIGAR_OVERRUN: c_int = -2;
 
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
 /// (src/reads/alignment_utils.rs:52-58, src/model/allele_likelihoods.rs:17)
@@ -757,12 +762,60 @@ extern "C" {
         hap_event_alt: *mut u8,
         hap_event_type: *mut u32,
     ) -> c_int;
+    /// the activity profile (haplotype_caller_engine.rs:627-1107, band_pass_activity_profile.rs): per (window, sample, position)
+    /// the RefVsAnyResult, per position the soft-clip average and is_active_prob (f32), per profile the band-passed state list
+    /// (f32); every output but window_status may be null
+    pub fn phmm_activity_profile(
+        h: *mut phmm_handle,
+        n_windows: u32,
+        n_samples: u32,
+        ploidy: u32,
+        min_base_quality: u32,
+        ref_pseudo_count: f64,
+        snp_pseudo_count: f64,
+        indel_pseudo_count: f64,
+        stand_min_conf: f64,
+        max_prob_propagation: u32,
+        max_filter_size: u32,
+        sigma: f64,
+        adaptive_filter_size: c_int,
+        profile_size: u32,
+        window_start: *const u64,
+        window_len: *const u32,
+        window_contig_length: *const u64,
+        window_ref_off: *const u32,
+        ref_bases: *const u8,
+        group_read_off: *const u32,
+        read_pos: *const i64,
+        read_cigar_off: *const u32,
+        read_cigar: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_quals: *const u8,
+        window_status: *mut i32,
+        read_counts: *mut u32,
+        ref_depth: *mut u32,
+        non_ref_depth: *mut u32,
+        gl: *mut f64,
+        pl: *mut i32,
+        soft_clip_mean: *mut f64,
+        soft_clip_count: *mut u32,
+        qual: *mut f64,
+        af_flags: *mut u32,
+        is_active_prob: *mut c_void,
+        filter_size: *mut u32,
+        profile_prob: *mut c_void,
+        profile_len: *mut u32,
+    ) -> c_int;
+    /// (parity tests: the host-made Gaussian kernel and the per-(is_alt, quality) addends of the activity profile)
+    pub fn phmm_activity_band_kernel(max_filter_size: u32, sigma: f64, adaptive_filter_size: c_int, filter_size: *mut u32, kernel: *mut f64) -> c_int;
+    pub fn phmm_activity_term_table(ploidy: u32, term: *mut f64) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

@@ -5,6 +5,7 @@ Only what the path needs lives here: `csrc/` (gfx950 kernels + the C ABI of incl
 the host-side mirror of the reference interface.  Importing the package does not need a GPU;
 creating an engine does (there is no CPU fallback).
 """
+from .activity import activity_profile  # noqa: F401
 from .batch import Read, RegionBatch  # noqa: F401
 from .engine import HipPairHMMEngine, PhmmError  # noqa: F401
 from .events import discover_events  # noqa: F401

@@ -40,6 +40,8 @@ PHMM_ANN_NO_AD, PHMM_ANN_NO_QD, PHMM_ANN_QD_JITTER = 1, 2, 4
 PHMM_EVENTS_MAX_REF, PHMM_EVENTS_MAX_HAPS = 16384, 512
 PHMM_EV_HAP_IN_TWO_ALLELES = 1
 PHMM_EV_TYPE_SNP, PHMM_EV_TYPE_MNP, PHMM_EV_TYPE_INDEL = 1, 2, 3
+PHMM_ACTIVITY_MAX_PLOIDY, PHMM_ACTIVITY_MAX_FILTER = 64, 65536
+PHMM_ACT_STATUS_REF_SKIP, PHMM_ACT_STATUS_CIGAR_OVERRUN = -1, -2
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
 
 class EngineConfig(C.Structure):
@@ -150,6 +152,12 @@ SYMBOLS = [
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), u32p, C.POINTER(C.c_int32), u32p, u8p, u32p, u8p, u32p,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), u32p, u32p, u8p, u32p]),
+    ("phmm_activity_profile", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_uint32, u64p, u32p, u64p, u32p, u8p,
+                                        u32p, C.POINTER(C.c_int64), u32p, u32p, u32p, u8p, u8p, C.POINTER(C.c_int32), u32p, u32p, u32p,
+                                        f64p, C.POINTER(C.c_int32), f64p, u32p, f64p, u32p, C.c_void_p, u32p, C.c_void_p, u32p]),
+    ("phmm_activity_band_kernel", C.c_int, [C.c_uint32, C.c_double, C.c_int, u32p, f64p]),
+    ("phmm_activity_term_table", C.c_int, [C.c_uint32, f64p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),

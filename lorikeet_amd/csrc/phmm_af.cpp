@@ -24,9 +24,43 @@ int fail(phmm_handle *h, const std::string &msg) {
 // MathUtils::log10_factorial (math_utils.rs:133-135): ln_gamma(n + 1) * LOG10_E
 double log10_factorial(double n) { return std::lgamma(n + 1.0) * std::log10(M_E); }
 
-uint32_t genotypes_per_lane(uint32_t G) { return G <= 64 ? 1 : G <= 256 ? 4 : G <= 512 ? 8 : 16; }
+uint32_t genotypes_per_lane(uint32_t G) { return af_genotypes_per_lane(G); }
 
 }  // namespace
+
+namespace phmm {
+
+uint32_t af_genotypes_per_lane(uint32_t G) { return G <= 64 ? 1 : G <= 256 ? 4 : G <= 512 ? 8 : 16; }
+
+bool af_is_block_event(uint32_t G, uint32_t n_samples) {
+    uint32_t S = 64;
+    if (af_genotypes_per_lane(G) == 1) {
+        S = 1;
+        while (S < G) S <<= 1;
+    }
+    return (n_samples + 64 / S - 1) / (64 / S) >= AF_BLOCK_PASSES;
+}
+
+AfGenotypeTables af_genotype_tables(const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &T, uint32_t ploidy) {
+    AfGenotypeTables t;
+    const size_t n_gt = T.first.size() - 1;
+    t.log10_comb.resize(n_gt);
+    t.gt_alleles.assign(n_gt, 0);
+    const double log10_ploidy_factorial = log10_factorial((double)ploidy);
+    for (size_t g = 0; g < n_gt; ++g) {
+        double s = 0.0;
+        for (uint32_t c = T.first[g]; c < T.first[g + 1]; ++c) {
+            s += log10_factorial((double)(T.second[c] >> 16));
+            t.gt_alleles[g] |= 1ull << (T.second[c] & 0xffffu);
+        }
+        t.log10_comb[g] = log10_ploidy_factorial - s;  // GenotypeAlleleCounts::log10_combination_count
+    }
+    t.neg_log10_alleles.assign(AF_MAX_ALLELES + 1, 0.0);
+    for (uint32_t a = 1; a <= AF_MAX_ALLELES; ++a) t.neg_log10_alleles[a] = -std::log10((double)a);
+    return t;
+}
+
+}  // namespace phmm
 
 extern "C" {
 
@@ -95,19 +129,9 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
         // ---- the genotypes of (ploidy, most alleles): the index order of fewer alleles is a prefix of it ------------------
         const auto &T = genotype_table_of(h, ploidy, max_alleles);
         const size_t n_gt = T.first.size() - 1;
-        std::vector<double> log10_comb(n_gt);
-        std::vector<uint64_t> gt_alleles(n_gt, 0);
-        const double log10_ploidy_factorial = log10_factorial((double)ploidy);
-        for (size_t g = 0; g < n_gt; ++g) {
-            double s = 0.0;
-            for (uint32_t c = T.first[g]; c < T.first[g + 1]; ++c) {
-                s += log10_factorial((double)(T.second[c] >> 16));
-                gt_alleles[g] |= 1ull << (T.second[c] & 0xffffu);
-            }
-            log10_comb[g] = log10_ploidy_factorial - s;  // GenotypeAlleleCounts::log10_combination_count
-        }
-        std::vector<double> neg_log10_alleles(AF_MAX_ALLELES + 1, 0.0);
-        for (uint32_t a = 1; a <= AF_MAX_ALLELES; ++a) neg_log10_alleles[a] = -std::log10((double)a);
+        const AfGenotypeTables GT = af_genotype_tables(T, ploidy);
+        const std::vector<double> &log10_comb = GT.log10_comb, &neg_log10_alleles = GT.neg_log10_alleles;
+        const std::vector<uint64_t> &gt_alleles = GT.gt_alleles;
 
         // ---- the computed events, densely: alleles with their prior pseudo counts, PLs ------------------------------------
         std::vector<uint32_t> c_allele_off(n_c + 1, 0), c_G(n_c);
@@ -141,13 +165,7 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
             for (int block = 0; block < 2; ++block) {
                 for (uint32_t i = 0; i < n_c; ++i) {
                     if (genotypes_per_lane(c_G[i]) != classes[c]) continue;
-                    uint32_t S = 64;
-                    if (classes[c] == 1) {
-                        S = 1;
-                        while (S < c_G[i]) S <<= 1;
-                    }
-                    const uint32_t passes = (n_samples + 64 / S - 1) / (64 / S);
-                    if ((passes >= AF_BLOCK_PASSES) == (block == 1)) work.push_back(i);
+                    if (af_is_block_event(c_G[i], n_samples) == (block == 1)) work.push_back(i);
                 }
                 cls_off[c][1 + block] = (uint32_t)work.size() - cls_off[c][0] - (block ? cls_off[c][1] : 0);
             }

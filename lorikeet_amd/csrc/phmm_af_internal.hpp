@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 namespace phmm {
 
@@ -45,5 +47,17 @@ struct AfParams {
 
 // K genotypes per lane: 1 (G <= 64), 4 (G <= 256), 8 (G <= 512) or 16 (G <= 1 024)
 hipError_t launch_af(const AfParams &p, uint32_t genotypes_per_lane, hipStream_t stream);
+
+// Host side (phmm_af.cpp), shared by phmm_allele_frequency and phmm_activity_profile: what the kernel reads about the genotypes
+// of (ploidy, alleles) -- T is genotype_table_of's (component offsets, components) --, the genotypes a lane holds for G, and
+// whether an event of G genotypes and n_samples samples takes a workgroup (n_block_events) or a wave (n_wave_events).
+struct AfGenotypeTables {
+    std::vector<double> log10_comb;          // gt_log10_comb
+    std::vector<uint64_t> gt_alleles;
+    std::vector<double> neg_log10_alleles;   // [AF_MAX_ALLELES + 1]
+};
+AfGenotypeTables af_genotype_tables(const std::pair<std::vector<uint32_t>, std::vector<uint32_t>> &T, uint32_t ploidy);
+uint32_t af_genotypes_per_lane(uint32_t G);
+bool af_is_block_event(uint32_t G, uint32_t n_samples);
 
 }  // namespace phmm

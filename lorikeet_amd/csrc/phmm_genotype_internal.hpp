@@ -42,4 +42,16 @@ struct GenotypeParams {
 
 hipError_t launch_genotype(const GenotypeParams &p, hipStream_t stream);
 
+#ifdef __HIPCC__
+// gls_to_pls (genotype_likelihoods.rs:59-70): min((-10 * (gl - max)).round() as i32, i32::MAX), NaN -> 0, `as` saturates.  Shared
+// by the kernels that turn GLs into PLs (compile them with -ffp-contract=off).
+__device__ __forceinline__ int32_t to_pl(double gl, double adjust) {
+    const double v = round(-10.0 * (gl - adjust));
+    if (v != v) return 0;
+    if (v >= 2147483647.0) return 2147483647;
+    if (v <= -2147483648.0) return (-2147483647 - 1);
+    return (int32_t)v;
+}
+#endif
+
 }  // namespace phmm

@@ -45,15 +45,6 @@ __device__ __forceinline__ double component(double m, uint32_t c, const double *
     return c == 1 ? m : m + log10_k[c];
 }
 
-// genotype_likelihoods -> gls_to_pls: min((-10 * (gl - max)).round() as i32, i32::MAX), NaN -> 0, `as` saturates
-__device__ __forceinline__ int32_t to_pl(double gl, double adjust) {
-    const double v = round(-10.0 * (gl - adjust));
-    if (v != v) return 0;
-    if (v >= 2147483647.0) return 2147483647;
-    if (v <= -2147483648.0) return (-2147483647 - 1);
-    return (int32_t)v;
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(GT_THREADS) phmm_genotype_kernel(GenotypeParams p) {

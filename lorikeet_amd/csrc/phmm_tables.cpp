@@ -79,6 +79,66 @@ const std::vector<double> &table_match_to_match() { return tables().mm; }
 double initial_condition() { return std::pow(2.0, 1020.0); }                       // pair_hmm.rs:16
 double initial_condition_log10() { return std::log10(std::pow(2.0, 1020.0)); }    // pair_hmm.rs:17
 
+std::vector<double> activity_term_table(unsigned ploidy) {
+    const Tables &t = tables();
+    const size_t G = (size_t)ploidy + 1;
+    const double log10ploidy = std::log10((double)ploidy);
+    std::vector<double> term(2 * 256 * G);
+    for (int alt = 0; alt < 2; ++alt)
+        for (int q = 0; q < 256; ++q) {
+            // QualityUtils::qual_to_prob_log10 and qual_to_error_prob_log10 + (-(3.0_f64.log10())) (quality_utils.rs:37-44)
+            const double right = std::log10(1.0 - std::pow(10.0, ((double)q) / -10.0));
+            const double wrong = (double)q * -0.1 + (-(std::log10(3.0)));
+            const double ref_likelihood = alt ? wrong : right, non_ref_likelihood = alt ? right : wrong;
+            double *row = term.data() + ((size_t)alt * 256 + (size_t)q) * G;
+            row[0] = ref_likelihood + log10ploidy;
+            row[G - 1] = non_ref_likelihood + log10ploidy;
+            size_t i = 1, j = G - 2;
+            while (i < G - 1) {
+                row[i] = approx_log10_sum_log10(t, ref_likelihood + std::log10((double)j), non_ref_likelihood + std::log10((double)i));
+                i += 1;
+                j -= 1;
+            }
+        }
+    return term;
+}
+
+const std::vector<float> &activity_prob_of_qual() {
+    static const std::vector<float> table = [] {
+        std::vector<float> v(256);
+        for (int q = 0; q < 256; ++q) v[q] = (float)(1.0 - std::pow(10.0, ((double)q) / -10.0));
+        return v;
+    }();
+    return table;
+}
+
+std::vector<double> activity_gaussian_kernel(size_t filter_size, double sigma) {
+    const double root_two_pi = std::sqrt(2.0 * 3.14159265358979323846264338327950288);  // math_utils.rs:22
+    const double mean = (double)filter_size;
+    std::vector<double> kernel(2 * filter_size + 1);
+    // MathUtils::normal_distribution (math_utils.rs:383-391)
+    for (size_t i = 0; i < kernel.size(); ++i) {
+        const double x = (double)i;
+        kernel[i] = std::exp(-(x - mean) * (x - mean) / (2.0 * sigma * sigma)) / (sigma * root_two_pi);
+    }
+    // MathUtils::normalize_sum_to_one (:402-415): a sequential sum
+    double sum = 0.0;
+    for (double v : kernel) sum += v;
+    if (!(sum >= 0.0)) return {};
+    for (double &v : kernel) v = v / sum;
+    return kernel;
+}
+
+unsigned activity_filter_size(const std::vector<double> &kernel, double min_prob_to_keep_in_filter) {
+    const size_t middle = (kernel.size() - 1) / 2;
+    size_t filter_end = middle;
+    while (filter_end > 0) {
+        if (kernel[filter_end - 1] < min_prob_to_keep_in_filter) break;
+        filter_end -= 1;
+    }
+    return (unsigned)(middle - filter_end);
+}
+
 
 // PairHMMLikelihoodCalculationEngine::initialize_pcr_error_model / get_error_model_adjusted_qual
 // (pair_hmm_likelihood_calculation_engine.rs:169-193): max(6, (40 - exp(len / (rate * pi)) + 1) as usize) as u8,

@@ -17,6 +17,8 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
                  "phmm_annotate_internal.hpp", "phmm_annotate_kernels.hip", "phmm_assign_internal.hpp",
                  "phmm_assign_kernels.hip"),
     "events": ("phmm_events_internal.hpp", "phmm_events_kernels.hip"),
+    "activity": ("phmm_activity_internal.hpp", "phmm_activity_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip",
+                 "phmm_genotype_internal.hpp"),
 }
 
 
