@@ -977,6 +977,112 @@ int phmm_activity_band_kernel(uint32_t max_filter_size, double sigma, int adapti
 int phmm_activity_term_table(uint32_t ploidy, double *term);
 
 /*
+ * phmm_finalize_reads -- what the reference does to a region's reads before it assembles and again before it genotypes, for
+ * many (region, sample) groups in one call: AssemblyBasedCallerUtils::finalize_regions up to its first sort
+ * (src/assembly/assembly_based_caller_utils.rs:97-172) with clean_overlapping_read_pairs (:263-289), and
+ * AssemblyRegion::trim_with_padded_span's map + filter (src/assembly/assembly_region.rs:341-352).  Restated as written:
+ * ReadClipper (src/reads/read_clipper.rs:63-530), ClippingOp::apply_hard_clip_bases / apply_revert_soft_clipped_bases
+ * (src/reads/clipping_op.rs:100-139, :201-235), CigarUtils::clip_cigar / revert_soft_clips / alignment_start_shift
+ * (src/reads/cigar_utils.rs:149-330), ReadUtils (src/reads/read_utils.rs:103-148, :190-211, :288-364), BirdToolRead::get_start /
+ * get_end / get_soft_start (src/reads/bird_tool_reads.rs:76-104, :239-249), FragmentCollection::create
+ * (src/utils/fragment_collection.rs:32-76), adjust_quals_of_overlapping_paired_fragments (src/utils/fragment_utils.rs:27-149).
+ * Everything runs on the device; a missing kernel is an error, there is no host path.
+ *
+ * cfg->steps (PHMM_FIN_*): a step that is not set is the identity, and the conditions between the steps stay in every
+ * combination -- get_start() <= get_end(), !is_unmapped before the adaptor step, !is_empty && seq_len_from_cigar > 0 before the
+ * region step, the final overlap test.  PHMM_FIN_ALL is finalize_regions; PHMM_FIN_REGION alone is trim_with_padded_span.
+ *   PHMM_FIN_SOFT_CLIPS     hard_clip_soft_clipped_bases when cfg->dont_use_soft_clipped_bases or the read has no well-defined
+ *                           fragment size, else revert_soft_clipped_bases (:124-131)
+ *   PHMM_FIN_LOW_QUAL_ENDS  hard_clip_low_qual_ends(cfg->min_tail_quality): the caller passes
+ *                           MIN_TAIL_QUALITY_WITH_ERROR_CORRECTION (6) with --error-correct-reads, else
+ *                           min-base-quality.saturating_sub(1) (:109-113, :308-309)
+ *   PHMM_FIN_ADAPTOR        hard_clip_adaptor_sequence
+ *   PHMM_FIN_REGION         hard_clip_to_region(group_span_start, group_span_end)
+ *   PHMM_FIN_PAIRS          the base qualities of overlapping mates; cfg->half_of_pcr_snv_qual (the reference: 20,
+ *                           fragment_utils.rs:9-14).  Needs mate_index.
+ * Per group g (one region, one sample): group_read_off [n_groups+1], group_span_start / group_span_end [n_groups]: the padded
+ * span the reference passes (region.get_padded_span(), both ends as the reference holds them).
+ * cfg points to a phmm_finalize_config and read_flags to uint16_t [n_reads]; both are declared `const void *` like the float
+ * arrays of phmm_activity_profile, so that the prototype keeps to the scalar types every binding of this header knows.
+ * Per read: read_pos (0-based), read_flags (BAM flags, uint16_t), read_mapq, read_mpos, read_isize, read_cigar_off [n_reads+1] /
+ * read_cigar (BAM-encoded), read_off [n_reads+1] / read_bases / read_quals, mate_index (or the whole array NULL): the
+ * call-wide index of the one other read of the same group with the same name, -1 for none -- the caller holds the names, and
+ * clipping does not change them.  read_bases is read by PHMM_FIN_PAIRS alone and may be NULL without it.
+ * Outputs per read, in input order; every pointer except read_status may be NULL and is then neither written nor copied back
+ * (out_cigar needs out_cigar_off and n_out_cigar):
+ *   read_status    0, or negative where the reference would panic (PHMM_FIN_STATUS_*); then keep = 0, the other per-read outputs
+ *                  are 0 and out_quals is the input's -- a panic of the pair step leaves the outputs of the clip steps as they
+ *                  were and sets keep = 0 and the status of both reads.  Nothing else in the call is affected.  Debug-build
+ *                  arithmetic decides what panics; a release build of the reference would wrap instead.
+ *                    PHMM_FIN_STATUS_CIGAR        a CigarBuilder result the reference unwraps is an Err (clip_cigar, revert_soft_clips)
+ *                    PHMM_FIN_STATUS_CLIP_RANGE   the three range panics of clip_by_reference_coordinates
+ *                    PHMM_FIN_STATUS_ARITHMETIC   a usize conversion or subtraction that fails: get_soft_start().unwrap() on a
+ *                                                 negative value, mpos as usize - 1, read.len() - (stop - start + 1)
+ *                    PHMM_FIN_STATUS_PAIR         an unwrap on None, or an index past a read, in the pair step
+ *                    PHMM_FIN_STATUS_WORKSPACE    more CIGAR elements than reserved (never with the room the call derives)
+ *   keep (u8)      what the reference's filter_map / filter decides (:148-167, assembly_region.rs:351)
+ *   new_pos        the read's position; the other outputs describe the read whether it is kept or not
+ *   out_unmapped (u8)   set for a read empty_read has touched (it is unmapped, its mate unmapped, mapq 0, no bases, no CIGAR)
+ *   clip_first, clip_len   clipping only ever removes bases from the two ends: the result's bases and qualities are the window
+ *                  [clip_first, clip_first + clip_len) of the input's.  No base is copied.
+ *   out_cigar_off [n_reads+1] (in): where each read's CIGAR goes in out_cigar, with room for the read's elements + 2 (a clip
+ *                  splits at most one element per end); out_cigar, n_out_cigar.  Room a read does not use is not written.
+ *   unclipped_len  AlignmentUtils::unclipped_read_length (src/reads/alignment_utils.rs:680-694); with read_mapq and the flags
+ *                  the caller applies the filters of haplotype_caller_engine.rs:1250-1273 without touching a CIGAR
+ *   lead_soft, trail_soft   the soft clip behind the leading hard clips and the one before the trailing hard clips: the pair
+ *                  phmm_region_compute takes as read_soft_clip
+ *   out_quals      (the layout of read_quals) the input qualities with the pair step's changes; bytes outside a read's window and
+ *                  reads not kept are copied unchanged
+ * Quirks kept: get_end() of an empty CIGAR is get_start(); clip_read clamps an operation's stop to the current length and skips
+ * one whose start is past it; the right-tail scan of clip_low_qual_ends never goes below index 0; a reverted read whose soft
+ * start is <= 0 loses 1 - soft_start bases and lands on position 0; hard_clip_to_region clips at ref_start.saturating_sub(1) /
+ * ref_stop + 1; hard_clip_both_ends clips the right tail first and empties the read when left > get_end() afterwards;
+ * clip_cigar drops a deletion that touches the cut; a read emptied by any step is unmapped from then on and skips the adaptor
+ * step; a read that came in flagged unmapped gets the CIGAR 0M from a hard clip; the pair step takes the read with the smaller
+ * soft start as the first one and the SECOND of the pair when the soft starts are equal.
+ * Pairs: FragmentCollection::create meets the two reads of a pair in the reference's sorted order.  The comparator's keys the
+ * device knows decide it, in this order: new_pos, reverse strand, flags, mapq, mpos, clipped length, then the lower input index.
+ * The reference compares names before flags -- mates share theirs -- and its unstable sort leaves complete ties open; here the
+ * lower index comes first.  A read is a pair candidate by fragment_collection.rs:47-51 evaluated on the clipped read; a candidate
+ * whose mate is not a kept candidate is a singleton.
+ * Out of scope, the caller's: the two par_sort_unstable calls, soft_clip_low_quality_ends (hidden flag, default off), BI / BD
+ * qualities (the reference does not clip them either, clipping_op.rs:233), the error corrector, the MAPQ / mate-contig filter.
+ * The output is the same from run to run and whatever else is in the batch (no atomics, one writer per element).
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): a required pointer NULL (cfg, the group
+ * arrays, the read arrays, read_status, mate_index with PHMM_FIN_PAIRS), unknown step bits, offsets that do not start at 0 or
+ * decrease, a CIGAR element with an operator above 8 or length 0, a CIGAR whose read length differs from the read's base count,
+ * span_end < span_start, positions from 2^62 on (read_pos negative included; mpos and isize by magnitude), less room in
+ * out_cigar_off than a read needs, a mate_index that is out of its group, self-referential or not symmetric.
+ * n_groups == 0, empty groups and reads of length 0 are fine.  One thread per handle.
+ */
+#define PHMM_FIN_SOFT_CLIPS 1u
+#define PHMM_FIN_LOW_QUAL_ENDS 2u
+#define PHMM_FIN_ADAPTOR 4u
+#define PHMM_FIN_REGION 8u
+#define PHMM_FIN_PAIRS 16u
+#define PHMM_FIN_ALL 31u
+#define PHMM_FIN_STATUS_CIGAR (-1)
+#define PHMM_FIN_STATUS_CLIP_RANGE (-2)
+#define PHMM_FIN_STATUS_ARITHMETIC (-3)
+#define PHMM_FIN_STATUS_PAIR (-4)
+#define PHMM_FIN_STATUS_WORKSPACE (-5)
+typedef struct phmm_finalize_config {
+    uint32_t steps;                      /* PHMM_FIN_* */
+    uint8_t min_tail_quality;
+    uint8_t dont_use_soft_clipped_bases;
+    uint8_t half_of_pcr_snv_qual;
+    uint8_t reserved;
+} phmm_finalize_config;
+int phmm_finalize_reads(phmm_handle *h, const void *cfg, uint32_t n_groups, const uint32_t *group_read_off,
+                        const uint64_t *group_span_start, const uint64_t *group_span_end, const int64_t *read_pos,
+                        const void *read_flags, const uint8_t *read_mapq, const int64_t *read_mpos, const int64_t *read_isize,
+                        const uint32_t *read_cigar_off, const uint32_t *read_cigar, const uint32_t *read_off,
+                        const uint8_t *read_bases, const uint8_t *read_quals, const int32_t *mate_index,
+                        const uint64_t *out_cigar_off, int32_t *read_status, uint8_t *keep, int64_t *new_pos, uint8_t *out_unmapped,
+                        uint32_t *clip_first, uint32_t *clip_len, uint32_t *out_cigar, uint32_t *n_out_cigar,
+                        uint32_t *unclipped_len, uint32_t *lead_soft, uint32_t *trail_soft, uint8_t *out_quals);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):
@@ -1015,7 +1121,7 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name);
  * the server to leave the chip first.  tools/server_trace.cpp prints a call's timeline from it. */
 uint32_t phmm_server_trace(int device_id, void *out, uint32_t cap);
 
-/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
+/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
  * family (tools/source_hash.py) at compile time.  smoke() and bench.py compare it with the tree they run in. */
 const char *phmm_build_info(void);
 

@@ -936,3 +936,141 @@ pub fn activity_profile(
     let depth = ref_depth.iter().zip(non_ref_depth.iter()).map(|(a, b)| a + b).collect();
     ActivityOutput { window_status, depth, soft_clip_mean, is_active_prob, profiles }
 }
+
+/// One read of `finalize_reads`: what the clip steps and the pair step read of a BAM record.  `mate` is the index inside the
+/// group of the other read with the same name.
+pub struct FinalizeRead<'a> {
+    pub pos: i64,
+    pub flags: u16,
+    pub mapq: u8,
+    pub mpos: i64,
+    pub isize: i64,
+    pub cigar: Vec<u32>,
+    pub bases: &'a [u8],
+    pub quals: &'a [u8],
+    pub mate: Option<usize>,
+}
+
+/// One (region, sample) of `finalize_reads`: the padded span as `region.get_padded_span()` holds it, and the reads.
+pub struct FinalizeGroup<'a> {
+    pub span: (u64, u64),
+    pub reads: Vec<FinalizeRead<'a>>,
+}
+
+/// What `finalize_reads` returns per read, in input order.  A kept read's bases are `bases[clip_first..clip_first + clip_len]`
+/// of its input, its qualities the same window of `quals`; `status` is negative where the reference would panic (then `keep`
+/// is false).
+pub struct FinalizedRead {
+    pub status: i32,
+    pub keep: bool,
+    pub pos: i64,
+    pub unmapped: bool,
+    pub clip_first: usize,
+    pub clip_len: usize,
+    pub cigar: Vec<u32>,
+    pub unclipped_len: usize,
+    pub soft_clip: (u32, u32),
+    pub quals: Vec<u8>,
+}
+
+/// `AssemblyBasedCallerUtils::finalize_regions` up to its first sort with `clean_overlapping_read_pairs`
+/// (src/assembly/assembly_based_caller_utils.rs:97-172, :263-289) for a batch of (region, sample) groups -- or, with `steps` =
+/// `PHMM_FIN_REGION`, the map + filter of `AssemblyRegion::trim_with_padded_span` (src/assembly/assembly_region.rs:341-352).
+/// The two sorts stay with the caller.
+pub fn finalize_reads(groups: &[FinalizeGroup], steps: u32, min_tail_quality: u8, dont_use_soft_clipped_bases: bool) -> Vec<FinalizedRead> {
+    let cfg = phmm_finalize_config {
+        steps,
+        min_tail_quality,
+        dont_use_soft_clipped_bases: dont_use_soft_clipped_bases as u8,
+        half_of_pcr_snv_qual: 20,
+        reserved: 0,
+    };
+    let span_start: Vec<u64> = groups.iter().map(|g| g.span.0).collect();
+    let span_end: Vec<u64> = groups.iter().map(|g| g.span.1).collect();
+    let (mut group_off, mut cigar_off, mut read_off): (Vec<u32>, Vec<u32>, Vec<u32>) = (vec![0], vec![0], vec![0]);
+    let mut out_cigar_off: Vec<u64> = vec![0];
+    let (mut pos, mut mpos, mut isize_): (Vec<i64>, Vec<i64>, Vec<i64>) = (Vec::new(), Vec::new(), Vec::new());
+    let mut flags: Vec<u16> = Vec::new();
+    let (mut mapq, mut bases, mut quals): (Vec<u8>, Vec<u8>, Vec<u8>) = (Vec::new(), Vec::new(), Vec::new());
+    let mut cigars: Vec<u32> = Vec::new();
+    let mut mate: Vec<i32> = Vec::new();
+    for g in groups {
+        let first = pos.len();
+        for r in &g.reads {
+            pos.push(r.pos);
+            flags.push(r.flags);
+            mapq.push(r.mapq);
+            mpos.push(r.mpos);
+            isize_.push(r.isize);
+            cigars.extend_from_slice(&r.cigar);
+            cigar_off.push(cigars.len() as u32);
+            out_cigar_off.push(out_cigar_off.last().unwrap() + r.cigar.len() as u64 + 2);
+            bases.extend_from_slice(r.bases);
+            quals.extend_from_slice(r.quals);
+            read_off.push(bases.len() as u32);
+            mate.push(r.mate.map(|m| (first + m) as i32).unwrap_or(-1));
+        }
+        group_off.push(pos.len() as u32);
+    }
+    let n = pos.len();
+    let mut status = vec![0i32; n];
+    let (mut keep, mut unmapped) = (vec![0u8; n], vec![0u8; n]);
+    let mut new_pos = vec![0i64; n];
+    let (mut clip_first, mut clip_len, mut n_out_cigar, mut unclipped_len) = (vec![0u32; n], vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+    let (mut lead_soft, mut trail_soft) = (vec![0u32; n], vec![0u32; n]);
+    let mut out_cigar = vec![0u32; *out_cigar_off.last().unwrap() as usize];
+    let mut out_quals = vec![0u8; quals.len()];
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_finalize_reads(
+                h,
+                &cfg as *const phmm_finalize_config as *const std::os::raw::c_void,
+                groups.len() as u32,
+                group_off.as_ptr(),
+                span_start.as_ptr(),
+                span_end.as_ptr(),
+                pos.as_ptr(),
+                flags.as_ptr() as *const std::os::raw::c_void,
+                mapq.as_ptr(),
+                mpos.as_ptr(),
+                isize_.as_ptr(),
+                cigar_off.as_ptr(),
+                cigars.as_ptr(),
+                read_off.as_ptr(),
+                bases.as_ptr(),
+                quals.as_ptr(),
+                mate.as_ptr(),
+                out_cigar_off.as_ptr(),
+                status.as_mut_ptr(),
+                keep.as_mut_ptr(),
+                new_pos.as_mut_ptr(),
+                unmapped.as_mut_ptr(),
+                clip_first.as_mut_ptr(),
+                clip_len.as_mut_ptr(),
+                out_cigar.as_mut_ptr(),
+                n_out_cigar.as_mut_ptr(),
+                unclipped_len.as_mut_ptr(),
+                lead_soft.as_mut_ptr(),
+                trail_soft.as_mut_ptr(),
+                out_quals.as_mut_ptr(),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP finalize_reads failed ({}): {}", rc, last_error(h));
+        }
+    });
+    (0..n)
+        .map(|r| FinalizedRead {
+            status: status[r],
+            keep: keep[r] != 0,
+            pos: new_pos[r],
+            unmapped: unmapped[r] != 0,
+            clip_first: clip_first[r] as usize,
+            clip_len: clip_len[r] as usize,
+            cigar: out_cigar[out_cigar_off[r] as usize..out_cigar_off[r] as usize + n_out_cigar[r] as usize].to_vec(),
+            unclipped_len: unclipped_len[r] as usize,
+            soft_clip: (lead_soft[r], trail_soft[r]),
+            quals: out_quals[read_off[r] as usize..read_off[r + 1] as usize].to_vec(),
+        })
+        .collect()
+}

@@ -113,6 +113,29 @@ pub const PHMM_ACTIVITY_MAX_PLOIDY: c_uint = 64;
 pub const PHMM_ACTIVITY_MAX_FILTER: c_uint = 65536;
 pub const PHMM_ACT_STATUS_REF_SKIP: c_int = -1;
 pub const PHMM_ACT_STATUS_CIGAR_OVERRUN: c_int = -2;
+/// `phmm_finalize_reads`: the steps (`phmm_finalize_config::steps`) and the statuses of reads the reference would panic on
+pub const PHMM_FIN_SOFT_CLIPS: c_uint = 1;
+pub const PHMM_FIN_LOW_QUAL_ENDS: c_uint = 2;
+pub const PHMM_FIN_ADAPTOR: c_uint = 4;
+pub const PHMM_FIN_REGION: c_uint = 8;
+pub const PHMM_FIN_PAIRS: c_uint = 16;
+pub const PHMM_FIN_ALL: c_uint = 31;
+pub const PHMM_FIN_STATUS_CIGAR: c_int = -1;
+pub const PHMM_FIN_STATUS_CLIP_RANGE: c_int = -2;
+pub const PHMM_FIN_STATUS_ARITHMETIC: c_int = -3;
+pub const PHMM_FIN_STATUS_PAIR: c_int = -4;
+pub const PHMM_FIN_STATUS_WORKSPACE: c_int = -5;
+
+/// `phmm_finalize_config`: which steps of `finalize_regions` run, and their parameters
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct phmm_finalize_config {
+    pub steps: u32,
+    pub min_tail_quality: u8,
+    pub dont_use_soft_clipped_bases: u8,
+    pub half_of_pcr_snv_qual: u8,
+    pub reserved: u8,
+}
 
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
 /// (src/reads/alignment_utils.rs:52-58, src/model/allele_likelihoods.rs:17)
@@ -810,12 +833,47 @@ extern "C" {
     /// (parity tests: the host-made Gaussian kernel and the per-(is_alt, quality) addends of the activity profile)
     pub fn phmm_activity_band_kernel(max_filter_size: u32, sigma: f64, adaptive_filter_size: c_int, filter_size: *mut u32, kernel: *mut f64) -> c_int;
     pub fn phmm_activity_term_table(ploidy: u32, term: *mut f64) -> c_int;
+    /// a region's reads finalized (assembly_based_caller_utils.rs:97-172, :263-289; assembly_region.rs:341-352): soft clips,
+    /// low-quality tails, adaptor, the clip to the padded span, the filter, the qualities of overlapping mates; every output
+    /// but read_status may be null.  `cfg` points to a `phmm_finalize_config`, `read_flags` to `[u16; n_reads]`
+    pub fn phmm_finalize_reads(
+        h: *mut phmm_handle,
+        cfg: *const c_void,
+        n_groups: u32,
+        group_read_off: *const u32,
+        group_span_start: *const u64,
+        group_span_end: *const u64,
+        read_pos: *const i64,
+        read_flags: *const c_void,
+        read_mapq: *const u8,
+        read_mpos: *const i64,
+        read_isize: *const i64,
+        read_cigar_off: *const u32,
+        read_cigar: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_quals: *const u8,
+        mate_index: *const i32,
+        out_cigar_off: *const u64,
+        read_status: *mut i32,
+        keep: *mut u8,
+        new_pos: *mut i64,
+        out_unmapped: *mut u8,
+        clip_first: *mut u32,
+        clip_len: *mut u32,
+        out_cigar: *mut u32,
+        n_out_cigar: *mut u32,
+        unclipped_len: *mut u32,
+        lead_soft: *mut u32,
+        trail_soft: *mut u32,
+        out_quals: *mut u8,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "activity=<hash> cigar=<hash> events=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

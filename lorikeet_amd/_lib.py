@@ -42,6 +42,8 @@ PHMM_EV_HAP_IN_TWO_ALLELES = 1
 PHMM_EV_TYPE_SNP, PHMM_EV_TYPE_MNP, PHMM_EV_TYPE_INDEL = 1, 2, 3
 PHMM_ACTIVITY_MAX_PLOIDY, PHMM_ACTIVITY_MAX_FILTER = 64, 65536
 PHMM_ACT_STATUS_REF_SKIP, PHMM_ACT_STATUS_CIGAR_OVERRUN = -1, -2
+PHMM_FIN_SOFT_CLIPS, PHMM_FIN_LOW_QUAL_ENDS, PHMM_FIN_ADAPTOR, PHMM_FIN_REGION, PHMM_FIN_PAIRS, PHMM_FIN_ALL = 1, 2, 4, 8, 16, 31
+PHMM_FIN_STATUS_CIGAR, PHMM_FIN_STATUS_CLIP_RANGE, PHMM_FIN_STATUS_ARITHMETIC, PHMM_FIN_STATUS_PAIR, PHMM_FIN_STATUS_WORKSPACE = -1, -2, -3, -4, -5
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
 
 class EngineConfig(C.Structure):
@@ -64,6 +66,12 @@ class RealignConfig(C.Structure):
     """phmm_realign_config (include/phmm.h)."""
     _fields_ = [("sw_parameters", SwParameters), ("overhang_strategy", C.c_int32), ("flags", C.c_uint32),
                 ("informative_threshold", C.c_double)]
+
+
+class FinalizeConfig(C.Structure):
+    """phmm_finalize_config (include/phmm.h)."""
+    _fields_ = [("steps", C.c_uint32), ("min_tail_quality", C.c_uint8), ("dont_use_soft_clipped_bases", C.c_uint8),
+                ("half_of_pcr_snv_qual", C.c_uint8), ("reserved", C.c_uint8)]
 
 
 class PlanInfo(C.Structure):
@@ -158,6 +166,10 @@ SYMBOLS = [
                                         f64p, C.POINTER(C.c_int32), f64p, u32p, f64p, u32p, C.c_void_p, u32p, C.c_void_p, u32p]),
     ("phmm_activity_band_kernel", C.c_int, [C.c_uint32, C.c_double, C.c_int, u32p, f64p]),
     ("phmm_activity_term_table", C.c_int, [C.c_uint32, f64p]),
+    ("phmm_finalize_reads", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u64p, u64p, C.POINTER(C.c_int64),
+                                      C.c_void_p, u8p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), u32p, u32p, u32p, u8p, u8p,
+                                      C.POINTER(C.c_int32), u64p, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int64), u8p, u32p, u32p, u32p,
+                                      u32p, u32p, u32p, u32p, u8p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),
