@@ -195,7 +195,8 @@ def test_calls_outside_the_servers_limits_take_the_launched_pipeline(eng):
 
 @pytest.mark.parametrize("hap_len,n_haps", [(450, 3), (512, 5), (401, 2), (16, 4), (33, 9)])
 def test_every_forward_geometry_of_the_server(eng, hap_len, n_haps):
-    """16 lanes per pair up to 400 bases, 32 beyond; one to three groups of haplotypes per read: equal to the launched pipeline."""
+    """A five-point smoke check -- 16 lanes per pair up to 400 bases, 32 beyond; one to three groups of haplotypes per read: equal to
+    the launched pipeline.  The sweep of every compiled instance, against the oracle, is tests/test_server_instances_hip.py."""
     b = synthetic.make_regions(2, 20, n_haps, hap_len, min(120, hap_len), seed=hap_len)
     extras = _uniform_extras(b, hap_len)
     mapq = np.full(b.n_reads, 60, np.uint8)
