@@ -750,7 +750,8 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
  *                   caller.  NO_QD (qd = 0) when the reference returns None: no log10_p_error, n_samples == 0, depth 0 (:302-315)
  * Integers are exact and the doubles bit-equal to the reference's operations (no contraction); nothing depends on the order
  * in which the device counts the reads.  PL subsetting and GT / GQ are phmm_assign_genotypes above (its sample_called goes in
- * here as it is); reverse_trim_alleles, phasing, fix_too_high_qd's draw and VCF output stay with the caller.
+ * here as it is); reverse_trim_alleles and phasing are phmm_phase_calls below; fix_too_high_qd's draw and the VCF strings stay
+ * with the caller.
  *   region_read_off ... event_hap_allele   as phmm_genotype_likelihoods
  *   mapq [n_reads]     as phmm_region_compute takes it
  *   call_allele_off [n_events+1], call_allele   the alleles of the call as indices into the event's alleles, strictly
@@ -853,7 +854,8 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
  * kept by the handle until phmm_destroy, a workspace of 25 bytes per haplotype base and CIGAR element (plus 200 per haplotype)
  * and 16 bytes per reference base -- about 70 MB for 1 024 regions of 8 haplotypes of 300 bases.
  * Out of scope, the caller's: remove_alt_alleles_if_too_many_genotypes (an event whose phmm_genotype_count(ploidy, A_e) exceeds
- * 1 024 is emitted as it is), given alleles (GGA mode), phasing, reverse_trim_alleles.
+ * 1 024 is emitted as it is), given alleles (GGA mode).  Phasing and reverse_trim_alleles are phmm_phase_calls below, which reads
+ * the haplotypes' event maps returned here.
  * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): a required array NULL (hap_event_off
  * non-NULL makes the other six map outputs required), offsets that do not start at 0 or are not monotonic, more than PHMM_EVENTS_MAX_REF reference bases or PHMM_EVENTS_MAX_HAPS haplotypes in a region, a contig length of 0,
  * a position from 2^62 on, a base outside "ACGTNacgtnRYKMSWBDHVU" (what the reference's allele constructor takes without
@@ -1083,6 +1085,86 @@ int phmm_finalize_reads(phmm_handle *h, const void *cfg, uint32_t n_groups, cons
                         uint32_t *unclipped_len, uint32_t *lead_soft, uint32_t *trail_soft, uint8_t *out_quals);
 
 /*
+ * phmm_phase_calls -- the tail of the reference's assign_genotype_likelihoods for many regions in ONE call: reverse_trim_alleles
+ * as make_annotated_call applies it, the called haplotypes, and physical phasing (phase_calls).  It reads the dense arrays as
+ * phmm_discover_events, phmm_annotate_events and phmm_assign_genotypes take and write them, so a caller chains discovery ->
+ * likelihoods -> AF -> assignment -> annotation -> phasing without rebuilding anything on the host.  Integers and bytes: every
+ * output EQUALS the reference's.  Per region, over its called events (C_e = call_allele_off[e+1] - call_allele_off[e] >= 1) in
+ * order:
+ *   1. reverse trim   make_annotated_call (src/haplotype/haplotype_caller_genotyping_engine.rs:451-489) trims a call only when
+ *                     C_e != A_e.  VariantContextUtils::trim_alleles(vc, false, true) (src/model/variant_context_utils.rs:
+ *                     956-1108) over AlignmentUtils::normalize_alleles(seqs, ranges, 0, true) (src/reads/alignment_utils.rs:
+ *                     585-675), as written: C_e <= 1, or any allele of length 1 that is not symbolic ('*' is one), leaves the
+ *                     call as it is; <NON_REF> is left out of the sequences and kept; all three loops of normalize_alleles run
+ *                     (the forward loop decides empty_allele and with it restore_one_base_at_end); the start does not move,
+ *                     call_rev_trim bases leave the end of every allele that is not symbolic, call_end = vc_start + len(ref) -
+ *                     call_rev_trim - 1.  The trimmed allele is the first length - call_rev_trim bytes: no base is copied.
+ *                     PHMM_PH_NO_TRIM in flags: no call is trimmed, phasing sees the alleles as given
+ *   2. called haplotypes   (:394-405) allele_mapper.remove(&idx) for idx in 0..C_e.  As written: the map is keyed by the MERGED
+ *                     context's allele index and idx is a POSITION in the call's list, so a call that kept alleles {0, 2} of
+ *                     three contributes the haplotypes of merged alleles 0 and 1.  Haplotype h is called iff
+ *                     0 <= event_hap_allele[e][h] < C_e for some called event e of its region
+ *   3. phase_calls    (src/assembly/assembly_based_caller_utils.rs:975-1348)
+ *                     construct_haplotype_mapping: a call with exactly one site-specific alternate allele (not the reference,
+ *                     not '*', not <NON_REF>) gets S_e = the called haplotypes whose event map holds an event with start ==
+ *                     vc_start[e] and an alternate allele equal, byte for byte, to the TRIMMED allele; every other call the empty
+ *                     set.  A merged alt that was extended by the reference's tail and not trimmed back matches nothing: as written
+ *                     construct_phase_set_mapping: total = |union of S_e|; for i < j with non-empty sets, "together" iff
+ *                     (|Si| == |Sj| and Sj within Si) or |Sj| == total, else "apart" iff |Si| + |Sj| == total and Si, Sj disjoint.
+ *                     The reference's middle clause of "together" tests call_haplotypes_available_for_phasing, which is created
+ *                     empty and only ever retain()ed: it is false for every non-empty Sj and restated as such, not repaired.
+ *                     On a related pair: i unmapped and j mapped clears the whole region's mapping and returns
+ *                     (PHMM_PH_ABORTED, nothing in the region is phased); both unmapped open group unique_counter, i 0|1 and
+ *                     j 0|1 (together) or 1|0 (apart); i mapped and j unmapped: j joins i's group with i's phase or the flipped
+ *                     one; both mapped: nothing
+ *                     construct_phase_groups / phase_vc: the group's first call in order leads it, PS is its start; every
+ *                     genotype of a member becomes phased; its allele list is reversed iff it is Het (determine_type: no no-call
+ *                     allele, two different alleles) and alleles[alt_allele_index] (1 for 0|1, 0 for 1|0) is not site-specific;
+ *                     && short-circuits, so ploidy 1 never indexes
+ * The reference has no test of phase_calls, trim_alleles or normalize_alleles: this restatement is pinned by reading.
+ * Inputs:
+ *   region_event_off, region_hap_off [n_regions+1]; event_allele_off; event_hap_allele; vc_start; allele_length; allele_kind
+ *   (PHMM_AF_KIND_*); allele_bases_off; allele_bases; hap_event_off [n_haps+1]; hap_event_start; hap_event_alt_off;
+ *   hap_event_alt       as phmm_discover_events writes them (with its per-haplotype event maps: ascending by start, one per start)
+ *   call_allele_off [n_events+1], call_allele   as phmm_annotate_events takes them; an empty list: the event is not called
+ *   n_samples, ploidy, gt [n_events x n_samples x ploidy]   phmm_assign_genotypes' gt; gt NULL skips the genotype stage, and
+ *                       is_phased and gt_phased must then be NULL too
+ *   flags               0 or PHMM_PH_NO_TRIM
+ * Outputs, per event unless noted; an event that is not called gets 0, and -1 in call_end, phase_group, phase_leader, phase_set
+ * and gt_phased:
+ *   call_rev_trim, call_end;  phase_n_haps = |S_e|;  hap_in_call (in event_hap_allele's layout, 1 iff the haplotype is in S_e;
+ *   NULL skips it);  phase_group (-1 = unphased, else the reference's unique_counter value within the region);  phase_gt
+ *   (PHMM_PH_GT_01 / PHMM_PH_GT_10);  phase_leader (the event index of the group's first call, -1 unphased: its start is PS, its
+ *   reference and first alt make the ID string);  phase_set (PS, -1 unphased);  region_alt_haps [n_regions] (total);
+ *   region_phase_flags [n_regions] (PHMM_PH_ABORTED);  is_phased [n_events x n_samples];  gt_phased [n_events x n_samples x
+ *   ploidy] (gt, reversed where phase_vc reverses).  The strings 0|1, 1|0 and the ID are the caller's to format.
+ * Precondition, not checked: a region's haplotypes differ by bases (the reference's HashSet<Haplotype> compares bases; the
+ * assembler's result set guarantees it).  Limits: PHMM_EVENTS_MAX_HAPS haplotypes per region (a set is 512 bits); events per
+ * region as phmm_discover_events.  Device workspace kept by the handle: 68 bytes per event and 64 per region.
+ * The result is the same from run to run and whatever else is in the batch: the one atomic is an OR, every other element has
+ * one writer.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): a required array NULL (gt without its two
+ * outputs, or they without gt), unknown flag bits, offsets that do not start at 0 or decrease, more than PHMM_EVENTS_MAX_HAPS
+ * haplotypes in a region, a call list that does not start with 0, is not strictly increasing or reaches A_e, an unknown kind, a
+ * reference allele that is not plain, a call allele that is not symbolic with length 0 or more bases than its slot, ploidy 0
+ * with gt given, a gt entry outside [-1, C_e), haplotype events that do not ascend by start.  n_regions == 0, regions without
+ * events and regions without haplotypes are fine.  One thread per handle.
+ */
+#define PHMM_PH_NO_TRIM 1u
+#define PHMM_PH_ABORTED 1u
+#define PHMM_PH_GT_01 0
+#define PHMM_PH_GT_10 1
+int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32_t *region_event_off, const uint32_t *region_hap_off,
+                     const uint32_t *event_allele_off, const int32_t *event_hap_allele, const int64_t *vc_start,
+                     const uint32_t *allele_length, const uint8_t *allele_kind, const uint32_t *allele_bases_off,
+                     const uint8_t *allele_bases, const uint32_t *hap_event_off, const int64_t *hap_event_start,
+                     const uint32_t *hap_event_alt_off, const uint8_t *hap_event_alt, const uint32_t *call_allele_off,
+                     const uint32_t *call_allele, uint32_t n_samples, uint32_t ploidy, const int32_t *gt, uint32_t flags,
+                     uint32_t *call_rev_trim, int64_t *call_end, uint32_t *phase_n_haps, uint8_t *hap_in_call,
+                     int32_t *phase_group, uint8_t *phase_gt, int32_t *phase_leader, int64_t *phase_set,
+                     uint32_t *region_alt_haps, uint32_t *region_phase_flags, uint8_t *is_phased, int32_t *gt_phased);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):
@@ -1121,7 +1203,7 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name);
  * the server to leave the chip first.  tools/server_trace.cpp prints a call's timeline from it. */
 uint32_t phmm_server_trace(int device_id, void *out, uint32_t cap);
 
-/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
+/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
  * family (tools/source_hash.py) at compile time.  smoke() and bench.py compare it with the tree they run in. */
 const char *phmm_build_info(void);
 

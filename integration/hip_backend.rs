@@ -1074,3 +1074,117 @@ pub fn finalize_reads(groups: &[FinalizeGroup], steps: u32, min_tail_quality: u8
         })
         .collect()
 }
+
+/// The arrays `phase_calls` reads, as `phmm_discover_events` (with its per-haplotype event maps), the AF step's call lists and
+/// `phmm_assign_genotypes` leave them; `gt` is `[n_events][n_samples][ploidy]` indices into the call's list, -1 a no-call allele.
+pub struct PhaseInput<'a> {
+    pub region_event_off: &'a [u32],
+    pub region_hap_off: &'a [u32],
+    pub event_allele_off: &'a [u32],
+    pub event_hap_allele: &'a [i32],
+    pub vc_start: &'a [i64],
+    pub allele_length: &'a [u32],
+    pub allele_kind: &'a [u8],
+    pub allele_bases_off: &'a [u32],
+    pub allele_bases: &'a [u8],
+    pub hap_event_off: &'a [u32],
+    pub hap_event_start: &'a [i64],
+    pub hap_event_alt_off: &'a [u32],
+    pub hap_event_alt: &'a [u8],
+    pub call_allele_off: &'a [u32],
+    pub call_allele: &'a [u32],
+    pub n_samples: usize,
+    pub ploidy: usize,
+    pub gt: &'a [i32],
+}
+
+/// What `phase_calls` returns per event, in input order.  `end` is the call's end after `reverse_trim_alleles`, the trimmed
+/// allele the first `length - rev_trim` bases of each allele that is not symbolic.  `group` is `None` for an unphased call;
+/// otherwise PGT is "0|1" (`phase_10 == false`) or "1|0", PS is `phase_set`, and PID is made of the start, the reference and
+/// the first alt of event `leader`.  `gt` holds the sample genotypes in the order `phase_vc` leaves them.
+pub struct PhasedCall {
+    pub rev_trim: usize,
+    pub end: i64,
+    pub n_haps: usize,
+    pub group: Option<usize>,
+    pub phase_10: bool,
+    pub leader: Option<usize>,
+    pub phase_set: i64,
+    pub is_phased: Vec<bool>,
+    pub gt: Vec<Vec<i32>>,
+}
+
+/// The tail of `assign_genotype_likelihoods` for a batch of regions: `reverse_trim_alleles` as `make_annotated_call` applies it,
+/// the called haplotypes, and `AssemblyBasedCallerUtils::phase_calls` (src/assembly/assembly_based_caller_utils.rs:975-1348).
+/// Returns the calls and, per region, whether its mapping was cleared.  The strings of PGT and PID are the caller's to format.
+pub fn phase_calls(input: &PhaseInput, trim: bool) -> (Vec<PhasedCall>, Vec<bool>) {
+    let n_regions = if input.region_event_off.is_empty() { 0 } else { input.region_event_off.len() - 1 };
+    let n_events = if n_regions > 0 { input.region_event_off[n_regions] as usize } else { 0 };
+    let ns = input.n_samples;
+    let pl = input.ploidy;
+    let mut rev_trim = vec![0u32; n_events];
+    let (mut end, mut phase_set) = (vec![0i64; n_events], vec![0i64; n_events]);
+    let mut n_haps = vec![0u32; n_events];
+    let (mut group, mut leader) = (vec![0i32; n_events], vec![0i32; n_events]);
+    let mut phase_gt = vec![0u8; n_events];
+    let (mut alt_haps, mut region_flags) = (vec![0u32; n_regions], vec![0u32; n_regions]);
+    let mut is_phased = vec![0u8; n_events * ns];
+    let mut gt_phased = vec![0i32; n_events * ns * pl];
+    assert_eq!(input.gt.len(), n_events * ns * pl);
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_phase_calls(
+                h,
+                n_regions as u32,
+                input.region_event_off.as_ptr(),
+                input.region_hap_off.as_ptr(),
+                input.event_allele_off.as_ptr(),
+                input.event_hap_allele.as_ptr(),
+                input.vc_start.as_ptr(),
+                input.allele_length.as_ptr(),
+                input.allele_kind.as_ptr(),
+                input.allele_bases_off.as_ptr(),
+                input.allele_bases.as_ptr(),
+                input.hap_event_off.as_ptr(),
+                input.hap_event_start.as_ptr(),
+                input.hap_event_alt_off.as_ptr(),
+                input.hap_event_alt.as_ptr(),
+                input.call_allele_off.as_ptr(),
+                input.call_allele.as_ptr(),
+                ns as u32,
+                pl as u32,
+                input.gt.as_ptr(),
+                if trim { 0 } else { PHMM_PH_NO_TRIM },
+                rev_trim.as_mut_ptr(),
+                end.as_mut_ptr(),
+                n_haps.as_mut_ptr(),
+                std::ptr::null_mut(),
+                group.as_mut_ptr(),
+                phase_gt.as_mut_ptr(),
+                leader.as_mut_ptr(),
+                phase_set.as_mut_ptr(),
+                alt_haps.as_mut_ptr(),
+                region_flags.as_mut_ptr(),
+                is_phased.as_mut_ptr(),
+                gt_phased.as_mut_ptr(),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP phase_calls failed ({}): {}", rc, last_error(h));
+        }
+    });
+    let calls = (0..n_events)
+        .map(|e| PhasedCall {
+            rev_trim: rev_trim[e] as usize,
+            end: end[e],
+            n_haps: n_haps[e] as usize,
+            group: if group[e] >= 0 { Some(group[e] as usize) } else { None },
+            phase_10: phase_gt[e] as i32 == PHMM_PH_GT_10,
+            leader: if leader[e] >= 0 { Some(leader[e] as usize) } else { None },
+            phase_set: phase_set[e],
+            is_phased: is_phased[e * ns..(e + 1) * ns].iter().map(|&x| x != 0).collect(),
+            gt: (0..ns).map(|s| gt_phased[(e * ns + s) * pl..(e * ns + s + 1) * pl].to_vec()).collect(),
+        })
+        .collect();
+    (calls, region_flags.iter().map(|&f| f & PHMM_PH_ABORTED != 0).collect())
+}

@@ -125,6 +125,11 @@ pub const PHMM_FIN_STATUS_CLIP_RANGE: c_int = -2;
 pub const PHMM_FIN_STATUS_ARITHMETIC: c_int = -3;
 pub const PHMM_FIN_STATUS_PAIR: c_int = -4;
 pub const PHMM_FIN_STATUS_WORKSPACE: c_int = -5;
+/// `phmm_phase_calls`: the flag that turns the reverse trim off, the region flag of a cleared mapping, the two phase groups
+pub const PHMM_PH_NO_TRIM: c_uint = 1;
+pub const PHMM_PH_ABORTED: c_uint = 1;
+pub const PHMM_PH_GT_01: c_int = 0;
+pub const PHMM_PH_GT_10: c_int = 1;
 
 /// `phmm_finalize_config`: which steps of `finalize_regions` run, and their parameters
 #[repr(C)]
@@ -868,12 +873,51 @@ extern "C" {
         trail_soft: *mut u32,
         out_quals: *mut u8,
     ) -> c_int;
+    /// the called events of many regions reverse-trimmed and phased (haplotype_caller_genotyping_engine.rs:394-405, :451-489;
+    /// variant_context_utils.rs:956-1108; assembly_based_caller_utils.rs:975-1348) on the arrays `phmm_discover_events` writes and
+    /// the call lists and GT of `phmm_annotate_events` / `phmm_assign_genotypes`; `gt`, `is_phased`, `gt_phased` are null
+    /// together, `hap_in_call` may be null
+    pub fn phmm_phase_calls(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_event_off: *const u32,
+        region_hap_off: *const u32,
+        event_allele_off: *const u32,
+        event_hap_allele: *const i32,
+        vc_start: *const i64,
+        allele_length: *const u32,
+        allele_kind: *const u8,
+        allele_bases_off: *const u32,
+        allele_bases: *const u8,
+        hap_event_off: *const u32,
+        hap_event_start: *const i64,
+        hap_event_alt_off: *const u32,
+        hap_event_alt: *const u8,
+        call_allele_off: *const u32,
+        call_allele: *const u32,
+        n_samples: u32,
+        ploidy: u32,
+        gt: *const i32,
+        flags: u32,
+        call_rev_trim: *mut u32,
+        call_end: *mut i64,
+        phase_n_haps: *mut u32,
+        hap_in_call: *mut u8,
+        phase_group: *mut i32,
+        phase_gt: *mut u8,
+        phase_leader: *mut i32,
+        phase_set: *mut i64,
+        region_alt_haps: *mut u32,
+        region_phase_flags: *mut u32,
+        is_phased: *mut u8,
+        gt_phased: *mut i32,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

@@ -157,7 +157,7 @@ struct phmm_handle {
         std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
     } gwork;
     // grow-only staging of phmm_allele_frequency (phmm_af.cpp), phmm_annotate_events (phmm_annotate.cpp), phmm_assign_genotypes (phmm_assign.cpp)
-    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging;
+    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging;
     // phmm_discover_events' device-only workspace (phmm_events.cpp): grow-only, no host mirror
     char *events_scratch = nullptr;
     size_t events_scratch_cap = 0;
@@ -165,6 +165,8 @@ struct phmm_handle {
     size_t activity_scratch_cap = 0;
     char *finalize_scratch = nullptr;  // phmm_finalize_reads: the reads' CIGAR slots and what the soft-clip step left of them, device only
     size_t finalize_scratch_cap = 0;
+    char *phase_scratch = nullptr;  // phmm_phase_calls: the haplotype bitsets of the regions and of the calls, device only
+    size_t phase_scratch_cap = 0;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

@@ -20,6 +20,7 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "activity": ("phmm_activity_internal.hpp", "phmm_activity_kernels.hip", "phmm_af_internal.hpp", "phmm_af_kernels.hip",
                  "phmm_genotype_internal.hpp"),
     "finalize": ("phmm_finalize_internal.hpp", "phmm_finalize_kernels.hip", "phmm_cigar_internal.hpp", "phmm_cigar_device.hpp"),
+    "phase": ("phmm_phase_internal.hpp", "phmm_phase_kernels.hip"),
 }
 
 
