@@ -1165,6 +1165,90 @@ int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32_t *region_
                      uint32_t *region_alt_haps, uint32_t *region_phase_flags, uint8_t *is_phased, int32_t *gt_phased);
 
 /*
+ * phmm_assembly_kmers -- what the reference's read-threading assembler decides from k-mers alone, in front of the graph, for
+ * many regions and several k in ONE call: the sequences add_read makes of each read, the non-unique k-mers, where each sequence
+ * starts threading and which positions it visits, how many k-mers kmer_to_vertex_map will hold, and the verdicts that reject a
+ * k before a vertex exists.  The graph itself -- vertices, edges, multiplicities, pruning, dangling ends, paths -- stays the
+ * caller's.  Integers and bytes: every output EQUALS the reference's.  R = src/read_threading/read_threading_graph.rs,
+ * A = src/read_threading/read_threading_assembler.rs, K = src/assembly/kmer.rs.  Per region and k, as written:
+ *   sequences    create_graph (A:924-1089) adds the reference as one sequence (start 0, stop len), then add_read per read
+ *                (R:341-390): each maximal run of bases with to_ascii_uppercase(base) != 'N' and qual >= min_base_quality
+ *                (R:400-403) of length >= k is a sequence (the whole read, start, stop).  An empty read adds nothing
+ *   non-unique   the union over the sequences of determine_non_unique_kmers (R:111-141, R:164-187), whose loop runs over
+ *                0 ..= stop - k: from 0, NOT from start.  A run scans the read's prefix in front of it, unusable bases included,
+ *                so a k-mer that holds an N or a low-quality base can be in the set.  Kept as written
+ *   equality     the reference's Kmer compares a 64-bit SipHash of the bytes and the length (K:73-89, K:154-158), case-sensitive.
+ *                This call compares BYTES: two different k-mers that collide in SipHash are equal there and not here
+ *   start        set_threading_start_only_at_existing_vertex(!recover_dangling_branches) (A:980) with the default, dangling
+ *                branch recovery on: a sequence starts at its first k-mer that is not non-unique (R:239-248).  find_start
+ *                (R:569-588): the reference starts at 0; a run searches start .. stop.saturating_sub(k), the bound EXCLUSIVE,
+ *                so its last k-mer is never a start.  thread_sequence (R:484-561) returns at once if the WHOLE sequence's
+ *                length is <= start_pos + k (a reference of exactly k bases threads nothing), else it visits start_pos ..= stop - k.
+ *                The other mode (start only at an existing vertex) depends on the order of threading and is not part of this call
+ *   vertex map   track_kmer (R:635-639) enters a k-mer when a vertex is created for it, unless it is non-unique or already
+ *                there; extend_chain_by_one (R:700-769) follows an edge or merges into the mapped vertex, the reference-source
+ *                k-mer excepted (R:613-618), which gets a fresh vertex that is not entered again.  So the map holds the distinct
+ *                k-mers that some sequence visits and that are not non-unique
+ *   verdicts     reference shorter than k: a failed result (A:935-938), PHMM_ASM_REF_SHORT, and every other output of that
+ *                (k, region) is 0 (ids UINT32_MAX); determine_non_unique_kmers(reference) not empty: PHMM_ASM_REF_NON_UNIQUE
+ *                (A:940-956; the caller may allow it, so everything else is still computed); is_low_quality_graph (R:261-263)
+ *                n_non_unique * 4 > n_tracked: PHMM_ASM_LOW_COMPLEXITY (pruning touches neither set)
+ * Inputs:
+ *   region_ref_off [n_regions+1], ref_bases      the regions' reference haplotypes, one behind the other
+ *   region_read_off [n_regions+1], read_off [n_reads+1], read_bases, read_quals    the regions' reads in input order
+ *   read_first, read_len [n_reads] or both NULL  the read IS bases [read_first, read_first + read_len) of its slot: what
+ *                phmm_finalize_reads returns as clip_first / clip_len, so its output feeds this call with no base copied
+ *   n_k, k [n_k]   1 <= n_k <= PHMM_ASM_MAX_K_VALUES, 1 <= k <= PHMM_ASM_MAX_K, ascending; the same list for every region
+ *   min_base_quality   the reference's default is 10
+ * Outputs:
+ *   flags, n_sequences, n_non_unique, n_tracked, n_distinct [n_k x n_regions]   PHMM_ASM_REF_* / LOW_COMPLEXITY; the reference
+ *                plus the runs of >= k bases (count + 1 of A:1004-1016); the size of the non-unique set; kmer_to_vertex_map.len()
+ *                after build_graph_if_necessary; the distinct k-mers over all scanned positions
+ *   ref_kmer_flags [n_k x region_ref_off[n_regions]], read_kmer_flags [n_k x read_off[n_reads]]   k-major planes over ref_bases
+ *                and read_bases as given, a byte per position p of a sequence.  A position is SCANNED if some
+ *                determine_non_unique_kmers loop reaches it: every p <= len - k of the reference, every p <= stop - k of a read
+ *                whose last run of >= k bases ends at stop.  PHMM_ASM_KMER_NON_UNIQUE: the k-mer at p is in the region's set;
+ *                _THREADED: thread_sequence visits p as part of some run; _THREAD_START: find_start returns p for its run
+ *                (for a reference of exactly k bases position 0 has _THREAD_START and not _THREADED); _FIRST: p is the first
+ *                occurrence of its bytes among the region's scanned positions, the reference first, then the reads in input
+ *                order, positions ascending.  0 where p is not scanned (p + k beyond the read included) and outside a window
+ *   ref_kmer_id, read_kmer_id   both NULL (not written) or the same planes as u32: dense ids in the order of _FIRST, equal
+ *                bytes equal ids within a (k, region), UINT32_MAX where the position is not scanned: what a host assembler keys
+ *                its vertex map with instead of hashing byte slices
+ * Limits: PHMM_ASM_MAX_REF_BASES per region's reference, PHMM_ASM_MAX_READ_BASES per read (its window),
+ * (reference bases + read bases) x n_k <= PHMM_ASM_MAX_POSITIONS (the workspace is indexed with 32 bits).  Device workspace kept
+ * by the handle: 45 bytes per base and k (53 when some sequence is longer than 1 024 bases and its own table leaves LDS), and
+ * 10 per base for the prefix hash and the runs.
+ * The result is the same from run to run and whatever else is in the batch: which position claims a slot of a table is a
+ * race that no output shows; the other atomics are minima, ORs and integer sums.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): n_k outside 1..PHMM_ASM_MAX_K_VALUES; a k
+ * outside 1..PHMM_ASM_MAX_K; k not ascending; min_base_quality above 255; read_first without read_len or the reverse; one id
+ * plane without the other; a required array NULL; region_ref_off, region_read_off or read_off that does not start at 0 or
+ * decreases; a window outside its read; a reference or a read above its limit; bases x n_k above PHMM_ASM_MAX_POSITIONS.
+ * n_regions == 0, regions without reads and empty reads are fine.  One thread per handle.  Switch "asm_fingerprint_bits"
+ * (tests): the tables' fingerprints keep that many bits, so probing and the byte comparison run on ordinary inputs; the
+ * outputs do not change.
+ */
+#define PHMM_ASM_MAX_K_VALUES 8u
+#define PHMM_ASM_MAX_K 255u
+#define PHMM_ASM_MAX_REF_BASES 16384u
+#define PHMM_ASM_MAX_READ_BASES 16384u
+#define PHMM_ASM_MAX_POSITIONS 536870912u
+#define PHMM_ASM_REF_SHORT 1u
+#define PHMM_ASM_REF_NON_UNIQUE 2u
+#define PHMM_ASM_LOW_COMPLEXITY 4u
+#define PHMM_ASM_KMER_NON_UNIQUE 1u
+#define PHMM_ASM_KMER_THREADED 2u
+#define PHMM_ASM_KMER_THREAD_START 4u
+#define PHMM_ASM_KMER_FIRST 8u
+int phmm_assembly_kmers(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
+                        const uint32_t *region_read_off, const uint32_t *read_off, const uint8_t *read_bases,
+                        const uint8_t *read_quals, const uint32_t *read_first, const uint32_t *read_len, uint32_t n_k,
+                        const uint32_t *k, uint32_t min_base_quality, uint32_t *flags, uint32_t *n_sequences,
+                        uint32_t *n_non_unique, uint32_t *n_tracked, uint32_t *n_distinct, uint8_t *ref_kmer_flags,
+                        uint8_t *read_kmer_flags, uint32_t *ref_kmer_id, uint32_t *read_kmer_id);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):
@@ -1177,6 +1261,7 @@ int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32_t *region_
  *                  "region_sw_all" (pairs up to which a lone launched call aligns every read against every haplotype beside the
  *                  PairHMM kernels: -1 by load, 0 never), "region_flag_wait", "region_pick_timeout_us", "region_debug_pick" (tests),
  *                  "mirror_canary", "region_own_queue" (environment only)
+ *   assembly       "asm_fingerprint_bits" (tests: the bits phmm_assembly_kmers keeps of a fingerprint, 0 = all 64)
  *   many callers   "route_shared" (opt-in: private handles' small calls through the shared combiner)
  * Value -1 / 0 = back to the planner's choice as documented there.  Not to be called while another thread computes on the handle.
  * Returns PHMM_ERR_INVALID_ARG for an unknown name.
@@ -1203,7 +1288,7 @@ uint64_t phmm_get_stat(phmm_handle *h, const char *name);
  * the server to leave the chip first.  tools/server_trace.cpp prints a call's timeline from it. */
 uint32_t phmm_server_trace(int device_id, void *out, uint32_t cap);
 
-/* What the library was built from: "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
+/* What the library was built from: "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>", the hashes of the kernel sources of each
  * family (tools/source_hash.py) at compile time.  smoke() and bench.py compare it with the tree they run in. */
 const char *phmm_build_info(void);
 

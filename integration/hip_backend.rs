@@ -1188,3 +1188,130 @@ pub fn phase_calls(input: &PhaseInput, trim: bool) -> (Vec<PhasedCall>, Vec<bool
         .collect();
     (calls, region_flags.iter().map(|&f| f & PHMM_PH_ABORTED != 0).collect())
 }
+
+/// One region's sequences for `assembly_kmers`: the reference haplotype and the reads with their base qualities, in the order
+/// `create_graph` adds them.
+pub struct AssemblyKmerRegion<'a> {
+    pub reference: &'a [u8],
+    pub reads: Vec<(&'a [u8], &'a [u8])>,
+}
+
+/// What `assembly_kmers` returns for one k of one region.  `ref_flags[p]` and `read_flags[r][p]` hold `PHMM_ASM_KMER_*`, a read's
+/// over its bases as given (0 outside its window); `ref_ids` / `read_ids` the dense k-mer ids (`u32::MAX`: the position is not
+/// scanned) a vertex map is keyed with -- empty when the call was made without ids.
+pub struct AssemblyKmers {
+    pub k: usize,
+    pub ref_short: bool,
+    pub ref_non_unique: bool,
+    pub low_complexity: bool,
+    pub n_sequences: usize,
+    pub n_non_unique: usize,
+    pub n_tracked: usize,
+    pub n_distinct: usize,
+    pub ref_flags: Vec<u8>,
+    pub ref_ids: Vec<u32>,
+    pub read_flags: Vec<Vec<u8>>,
+    pub read_ids: Vec<Vec<u32>>,
+}
+
+/// The k-mer stage of `ReadThreadingAssembler::create_graph` for a batch of regions and every k in `ks` (ascending): which k are
+/// rejected before a graph exists, and per position whether its k-mer is non-unique, threaded, a threading start, and its id.
+/// `windows`: per read in input order (first, len) -- the read IS that part of its bases, what `finalize_reads` returns as
+/// `clip_first` / `clip_len`, so no base is copied; `None`: the whole reads.  `ids`: the id planes are four fifths of the bytes
+/// that come back, so a first call over every k goes without them and a second one asks for the k that survive.
+/// Returns `[region][k]`.
+pub fn assembly_kmers(
+    regions: &[AssemblyKmerRegion],
+    ks: &[usize],
+    min_base_quality: u8,
+    windows: Option<&[(u32, u32)]>,
+    ids: bool,
+) -> Vec<Vec<AssemblyKmers>> {
+    let n_regions = regions.len();
+    let (mut region_ref_off, mut region_read_off, mut read_off) = (vec![0u32], vec![0u32], vec![0u32]);
+    let (mut ref_bases, mut read_bases, mut read_quals) = (Vec::<u8>::new(), Vec::<u8>::new(), Vec::<u8>::new());
+    for g in regions {
+        ref_bases.extend_from_slice(g.reference);
+        region_ref_off.push(ref_bases.len() as u32);
+        for (bases, quals) in g.reads.iter() {
+            assert_eq!(bases.len(), quals.len());
+            read_bases.extend_from_slice(bases);
+            read_quals.extend_from_slice(quals);
+            read_off.push(read_bases.len() as u32);
+        }
+        region_read_off.push((read_off.len() - 1) as u32);
+    }
+    let k32: Vec<u32> = ks.iter().map(|&k| k as u32).collect();
+    let n_k = k32.len();
+    let (n_ref, n_read) = (ref_bases.len(), read_bases.len());
+    let mut flags = vec![0u32; n_k * n_regions];
+    let (mut n_sequences, mut n_non_unique) = (vec![0u32; n_k * n_regions], vec![0u32; n_k * n_regions]);
+    let (mut n_tracked, mut n_distinct) = (vec![0u32; n_k * n_regions], vec![0u32; n_k * n_regions]);
+    let (mut ref_flags, mut read_flags) = (vec![0u8; n_k * n_ref], vec![0u8; n_k * n_read]);
+    let n_ids = if ids { n_k } else { 0 };
+    let (mut ref_ids, mut read_ids) = (vec![0u32; n_ids * n_ref], vec![0u32; n_ids * n_read]);
+    let read_first: Vec<u32> = windows.unwrap_or(&[]).iter().map(|w| w.0).collect();
+    let read_len: Vec<u32> = windows.unwrap_or(&[]).iter().map(|w| w.1).collect();
+    if let Some(w) = windows {
+        assert_eq!(w.len(), read_off.len() - 1);
+    }
+    let or_null = |v: &Vec<u32>| if windows.is_some() { v.as_ptr() } else { std::ptr::null() };
+    let ids_or_null = |v: &mut Vec<u32>| if ids { v.as_mut_ptr() } else { std::ptr::null_mut() };
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_assembly_kmers(
+                h,
+                n_regions as u32,
+                region_ref_off.as_ptr(),
+                ref_bases.as_ptr(),
+                region_read_off.as_ptr(),
+                read_off.as_ptr(),
+                read_bases.as_ptr(),
+                read_quals.as_ptr(),
+                or_null(&read_first),
+                or_null(&read_len),
+                n_k as u32,
+                k32.as_ptr(),
+                min_base_quality as u32,
+                flags.as_mut_ptr(),
+                n_sequences.as_mut_ptr(),
+                n_non_unique.as_mut_ptr(),
+                n_tracked.as_mut_ptr(),
+                n_distinct.as_mut_ptr(),
+                ref_flags.as_mut_ptr(),
+                read_flags.as_mut_ptr(),
+                ids_or_null(&mut ref_ids),
+                ids_or_null(&mut read_ids),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP assembly_kmers failed ({}): {}", rc, last_error(h));
+        }
+    });
+    (0..n_regions)
+        .map(|g| {
+            (0..n_k)
+                .map(|i| {
+                    let o = i * n_regions + g;
+                    let (r0, r1) = (region_ref_off[g] as usize, region_ref_off[g + 1] as usize);
+                    let reads = region_read_off[g] as usize..region_read_off[g + 1] as usize;
+                    let span = |r: usize| i * n_read + read_off[r] as usize..i * n_read + read_off[r + 1] as usize;
+                    AssemblyKmers {
+                        k: ks[i],
+                        ref_short: flags[o] & PHMM_ASM_REF_SHORT != 0,
+                        ref_non_unique: flags[o] & PHMM_ASM_REF_NON_UNIQUE != 0,
+                        low_complexity: flags[o] & PHMM_ASM_LOW_COMPLEXITY != 0,
+                        n_sequences: n_sequences[o] as usize,
+                        n_non_unique: n_non_unique[o] as usize,
+                        n_tracked: n_tracked[o] as usize,
+                        n_distinct: n_distinct[o] as usize,
+                        ref_flags: ref_flags[i * n_ref + r0..i * n_ref + r1].to_vec(),
+                        ref_ids: if ids { ref_ids[i * n_ref + r0..i * n_ref + r1].to_vec() } else { Vec::new() },
+                        read_flags: reads.clone().map(|r| read_flags[span(r)].to_vec()).collect(),
+                        read_ids: if ids { reads.clone().map(|r| read_ids[span(r)].to_vec()).collect() } else { Vec::new() },
+                    }
+                })
+                .collect()
+        })
+        .collect()
+}

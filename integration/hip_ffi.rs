@@ -130,6 +130,19 @@ pub const PHMM_PH_NO_TRIM: c_uint = 1;
 pub const PHMM_PH_ABORTED: c_uint = 1;
 pub const PHMM_PH_GT_01: c_int = 0;
 pub const PHMM_PH_GT_10: c_int = 1;
+/// `phmm_assembly_kmers`: its limits, the verdicts per (k, region), the flags per (k, position)
+pub const PHMM_ASM_MAX_K_VALUES: c_uint = 8;
+pub const PHMM_ASM_MAX_K: c_uint = 255;
+pub const PHMM_ASM_MAX_REF_BASES: c_uint = 16384;
+pub const PHMM_ASM_MAX_READ_BASES: c_uint = 16384;
+pub const PHMM_ASM_MAX_POSITIONS: c_uint = 536870912;
+pub const PHMM_ASM_REF_SHORT: c_uint = 1;
+pub const PHMM_ASM_REF_NON_UNIQUE: c_uint = 2;
+pub const PHMM_ASM_LOW_COMPLEXITY: c_uint = 4;
+pub const PHMM_ASM_KMER_NON_UNIQUE: c_uint = 1;
+pub const PHMM_ASM_KMER_THREADED: c_uint = 2;
+pub const PHMM_ASM_KMER_THREAD_START: c_uint = 4;
+pub const PHMM_ASM_KMER_FIRST: c_uint = 8;
 
 /// `phmm_finalize_config`: which steps of `finalize_regions` run, and their parameters
 #[repr(C)]
@@ -912,12 +925,39 @@ extern "C" {
         is_phased: *mut u8,
         gt_phased: *mut i32,
     ) -> c_int;
+    /// what the read-threading assembler decides from k-mers alone, for many regions and several k (read_threading_graph.rs:111-187,
+    /// :341-403, :484-639; read_threading_assembler.rs:935-956): verdicts and counts per (k, region), flags and dense ids per
+    /// (k, position); `read_first` / `read_len` are null together, and so are the two id planes
+    pub fn phmm_assembly_kmers(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_read_off: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_quals: *const u8,
+        read_first: *const u32,
+        read_len: *const u32,
+        n_k: u32,
+        k: *const u32,
+        min_base_quality: u32,
+        flags: *mut u32,
+        n_sequences: *mut u32,
+        n_non_unique: *mut u32,
+        n_tracked: *mut u32,
+        n_distinct: *mut u32,
+        ref_kmer_flags: *mut u8,
+        read_kmer_flags: *mut u8,
+        ref_kmer_id: *mut u32,
+        read_kmer_id: *mut u32,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "activity=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

@@ -45,6 +45,9 @@ PHMM_ACT_STATUS_REF_SKIP, PHMM_ACT_STATUS_CIGAR_OVERRUN = -1, -2
 PHMM_FIN_SOFT_CLIPS, PHMM_FIN_LOW_QUAL_ENDS, PHMM_FIN_ADAPTOR, PHMM_FIN_REGION, PHMM_FIN_PAIRS, PHMM_FIN_ALL = 1, 2, 4, 8, 16, 31
 PHMM_FIN_STATUS_CIGAR, PHMM_FIN_STATUS_CLIP_RANGE, PHMM_FIN_STATUS_ARITHMETIC, PHMM_FIN_STATUS_PAIR, PHMM_FIN_STATUS_WORKSPACE = -1, -2, -3, -4, -5
 PHMM_PH_NO_TRIM, PHMM_PH_ABORTED, PHMM_PH_GT_01, PHMM_PH_GT_10 = 1, 1, 0, 1
+PHMM_ASM_MAX_K_VALUES, PHMM_ASM_MAX_K, PHMM_ASM_MAX_REF_BASES, PHMM_ASM_MAX_READ_BASES, PHMM_ASM_MAX_POSITIONS = 8, 255, 16384, 16384, 536870912
+PHMM_ASM_REF_SHORT, PHMM_ASM_REF_NON_UNIQUE, PHMM_ASM_LOW_COMPLEXITY = 1, 2, 4
+PHMM_ASM_KMER_NON_UNIQUE, PHMM_ASM_KMER_THREADED, PHMM_ASM_KMER_THREAD_START, PHMM_ASM_KMER_FIRST = 1, 2, 4, 8
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
 
 class EngineConfig(C.Structure):
@@ -175,6 +178,8 @@ SYMBOLS = [
                                    u8p, u32p, C.POINTER(C.c_int64), u32p, u8p, u32p, u32p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
                                    C.c_uint32, u32p, C.POINTER(C.c_int64), u32p, u8p, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64), u32p, u32p, u8p, C.POINTER(C.c_int32)]),
+    ("phmm_assembly_kmers", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
+                                      u32p, u32p, u32p, u32p, u32p, u8p, u8p, u32p, u32p]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),

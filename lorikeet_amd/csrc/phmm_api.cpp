@@ -244,11 +244,12 @@ void phmm_destroy(phmm_handle *h) {
         if (h->arenas[i].host) (void)hipHostFree(h->arenas[i].host);
         if (h->arenas[i].rescue) (void)hipFree(h->arenas[i].rescue);
     }
-    for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging, &h->events_staging, &h->activity_staging, &h->finalize_staging, &h->phase_staging}) b->release();
+    for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging, &h->events_staging, &h->activity_staging, &h->finalize_staging, &h->phase_staging, &h->asm_staging}) b->release();
     if (h->events_scratch) (void)hipFree(h->events_scratch);
     if (h->activity_scratch) (void)hipFree(h->activity_scratch);
     if (h->finalize_scratch) (void)hipFree(h->finalize_scratch);
     if (h->phase_scratch) (void)hipFree(h->phase_scratch);
+    if (h->asm_scratch) (void)hipFree(h->asm_scratch);
     if (h->swork.slab) (void)hipFree(h->swork.slab);
     if (h->swork.ws) (void)hipFree(h->swork.ws);
     if (h->swork.ext) (void)hipFree(h->swork.ext);
@@ -1798,6 +1799,7 @@ int phmm_set_switch(phmm_handle *h, const char *name, int value) {
     else if (n == "region_debug_pick") w.region_debug_pick = value > 0 ? value : 0;
     else if (n == "mirror_canary") w.mirror_canary = value > 0 ? value : 0;
     else if (n == "route_shared") w.route_shared = value;
+    else if (n == "asm_fingerprint_bits") w.asm_fingerprint_bits = value > 0 && value < 64 ? value : 0;
     else if (n == "sw_lanes") w.sw_lanes = value == 8 || value == 16 || value == 32 || value == 64 ? value : 0;
     else {
         h->err = "phmm_set_switch: unknown switch";

@@ -80,6 +80,7 @@ struct Switches {
     int route_shared = 0;       // PHMM_ROUTE_SHARED (opt-in): while MORE than this many of the caller's handles are alive on a device, the one-shot calls
                                 // of private handles go through the device's shared combiner (its lanes) instead of their own streams -- 0 = never
     int mirror_canary = 0;      // PHMM_MIRROR_CANARY: 1 = late / stray device stores into the pinned mirror fail the call (Arena::canary_*), 2 = abort()
+    int asm_fingerprint_bits = 0;  // (tests) phmm_assembly_kmers keeps this many bits of a fingerprint, so equal fingerprints of different bytes happen; 0 = all 64
     int region_own_queue = 1;   // PHMM_REGION_OWN_QUEUE: 0 = one-enqueue calls stay on the handle's ordinary slot-0 stream (A/B)
     int region_server = -1;     // PHMM_REGION_SERVER: region calls go through the device's resident server (phmm_server.cpp) -- -1: the one-shot calls of
                                 // PRIVATE handles while more than five of the caller's handles are alive on the device (a handle whose other switches
@@ -157,7 +158,7 @@ struct phmm_handle {
         std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
     } gwork;
     // grow-only staging of phmm_allele_frequency (phmm_af.cpp), phmm_annotate_events (phmm_annotate.cpp), phmm_assign_genotypes (phmm_assign.cpp)
-    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging;
+    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging, asm_staging;
     // phmm_discover_events' device-only workspace (phmm_events.cpp): grow-only, no host mirror
     char *events_scratch = nullptr;
     size_t events_scratch_cap = 0;
@@ -167,6 +168,8 @@ struct phmm_handle {
     size_t finalize_scratch_cap = 0;
     char *phase_scratch = nullptr;  // phmm_phase_calls: the haplotype bitsets of the regions and of the calls, device only
     size_t phase_scratch_cap = 0;
+    char *asm_scratch = nullptr;  // phmm_assembly_kmers: prefix hashes, runs, the sequences' and the regions' k-mer tables, device only
+    size_t asm_scratch_cap = 0;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

@@ -21,6 +21,7 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
                  "phmm_genotype_internal.hpp"),
     "finalize": ("phmm_finalize_internal.hpp", "phmm_finalize_kernels.hip", "phmm_cigar_internal.hpp", "phmm_cigar_device.hpp"),
     "phase": ("phmm_phase_internal.hpp", "phmm_phase_kernels.hip"),
+    "asm": ("phmm_asm_internal.hpp", "phmm_asm_kernels.hip"),
 }
 
 
