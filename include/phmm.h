@@ -1249,6 +1249,113 @@ int phmm_assembly_kmers(phmm_handle *h, uint32_t n_regions, const uint32_t *regi
                         uint8_t *read_kmer_flags, uint32_t *ref_kmer_id, uint32_t *read_kmer_id);
 
 /*
+ * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
+ * assembler's haplotypes before a likelihood is computed, for many regions in ONE call: get_variation_events, the trimmer's
+ * two spans, every haplotype cut to the padded span, duplicates folded, the rest in the reference's order.  Integers and
+ * bytes: every output EQUALS the reference's.  T = src/assembly/assembly_region_trimmer.rs, H = src/haplotype/haplotype.rs,
+ * U = src/reads/alignment_utils.rs, S = src/assembly/assembly_result_set.rs, I = src/utils/simple_interval.rs.  Per region:
+ *   event maps   build_event_maps_for_haplotypes as phmm_discover_events step 1 restates it (the same kernel).  A haplotype
+ *                whose map fails gives the region its PHMM_EV_STATUS_* (the first such haplotype's): call_region returns the
+ *                empty model there (:1197-1204).  Every other output of that region is 0 / PHMM_TRIM_FATE_NOT_TRIMMED
+ *   spans        AssemblyRegionTrimmer::trim (T:61-131) with legacy_trimming = false, as call_region passes it.  Only events
+ *                whose span overlaps the active span count (I:201-205 through :341-343; the three clauses of I:245-249 say the
+ *                same of well-formed intervals); with none the region has no variation: variation_present 0, no output
+ *                haplotypes, spans 0.  variant span = [min start, max end] & active span; per event the padding is
+ *                padding[1] if its CACHED type is INDEL (a SNP joined with an insertion stays a SNP), else padding[0];
+ *                min(start.saturating_sub(padding)), max(end + padding), & the region's padded span.  The BTreeSet's order and
+ *                dedupe (src/model/variant_context.rs:69-82) change neither extreme: the device reduces over all haplotype events
+ *   STR padding  get_num_tandem_repeat_units (src/model/variant_context_utils.rs:32-79) returns Some only with NO alternate
+ *                allele (:74); an event of an event map has exactly one, so the arm that adds padding[2] (T:103-108) has no
+ *                input and no repeat scan runs.  Kept as written; tests/test_region_trim_oracle.py runs the function itself.
+ *                What the arm does do for every indel is slice the reference bases from start + 1 - padded span start
+ *                (src/annotator/tandem_repeat.rs:21-25): an indel that starts more than one base in front of the region's
+ *                padded span, or whose index lies behind the region's reference bases, panics there:
+ *                PHMM_TRIM_STATUS_REPEAT_SLICE, every other output of the region 0 / NOT_TRIMMED
+ *   new spans    trim_with_padded_span (src/assembly/assembly_region.rs:323-339): active & variant span, padded & padded
+ *                variant span.  They feed phmm_finalize_reads with PHMM_FIN_REGION as they are
+ *   trim         Haplotype::trim(new padded span) (H:149-236): the location must contain the span; new_start is measured from
+ *                hap_loc_start, NOT from hap_start_wrt_ref; get_bases_covering_ref_interval (U:759-843) with the start test in
+ *                front of the end test inside an M element, a deletion failing on either bound (CUT_IN_DELETION), an insertion
+ *                at the cut left out, the two tests behind the loop, min(stop + 1, len); no bases: EMPTY;
+ *                trim_cigar_by_reference (U:334-386, :853) through a builder that strips deletions at the ends; a leading or
+ *                trailing insertion of the result removed through a builder that does not; nothing left: ALL_INSERTION;
+ *                out_hap_start_wrt_ref = new_start + hap_start_wrt_ref.  The bases come out upper-cased (Haplotype::new,
+ *                src/model/byte_array_allele.rs:76), and equality and order below are of the upper-cased bytes.  The INPUT
+ *                bases are taken as given, as phmm_discover_events takes them: the event map compares raw bytes, so a lower-case
+ *                haplotype base against the same base in upper case in the reference is an event whose alleles collapse
+ *                (PHMM_EV_STATUS_ALLELES) where the reference, whose haplotypes are upper-cased when they are made, sees no
+ *                event.  A caller that may hold lower-case bases upper-cases haplotypes and reference first
+ *   panics       where the reference panics or returns Err the region's status is that of its FIRST such haplotype in input
+ *                order, the spans and PHMM_TRIM_VARIATION_SPAN stay, it has no output haplotypes, and no other region is
+ *                touched: PHMM_TRIM_STATUS_LOCATION  the location does not contain the span (H:159-163);  _LENGTH  bases and
+ *                CIGAR disagree (U:772-779);  _OPERATOR  the walk reaches an S (U:818-820; N, H and P fail the event map
+ *                first);  _NOT_FOUND  "Never found start or stop" (U:833-838; the CIGAR ends in front of the span);  _BUILDER
+ *                a CigarBuilder Err (U:374-377, H:215-222, cigar_builder.rs:321-325): an I behind a right soft clip that sits
+ *                just behind the span's end, 10M2S3I cut at its last matched base;  _REF_ELIMINATED  a haplotype with
+ *                hap_is_ref that trims to None (S:487-490)
+ *   order        trim_down_haplotypes (S:465-499) into a BTreeMap: equality by bases, order by length, then bytes unsigned
+ *                (H:269-284).  An equal later haplotype is dropped unless it is a reference haplotype, which replaces key and
+ *                value: a class is represented by its LAST member with hap_is_ref, else by its first member in input order, and
+ *                the representative's CIGAR, start and is_ref are emitted
+ *   variation    PHMM_TRIM_VARIATION_SPAN: the trimmer found variation (T:249-251).  PHMM_TRIM_VARIATION_SET: the result set's
+ *                variation_present after trim_to -- some input haplotype is not a reference haplotype (S:340), or some
+ *                representative is not (S:411-424); never cleared
+ * Inputs, per region: region_ref_off [n_regions+1], ref_bases, region_ref_start, region_hap_off [n_regions+1], hap_off, hap_bases,
+ *   hap_cigar_off, hap_cigar ((len << 4) | op), hap_start_wrt_ref, max_mnp_distance as phmm_discover_events takes them;
+ *   region_active_start / _end, region_padded_start / _end [n_regions] closed spans, the active one inside the padded one;
+ *   hap_loc_start / hap_loc_end [n_haps] the haplotype's genome location, closed;  hap_is_ref [n_haps] bytes;
+ *   padding [4]  SNP, indel and STR padding (the reference's defaults: 20, 75, 75) and max_extension_into_region_padding.  The
+ *                last two are carried for the ABI: the STR arm has no input (above), the legacy trimmer is not part of this call
+ * Outputs, per region [n_regions]: region_status (0, PHMM_EV_STATUS_*, PHMM_TRIM_STATUS_*); variation_present (PHMM_TRIM_VARIATION_*);
+ *   variant_start / _end, padded_start / _end the trimmer's two spans; new_active_start / _end, new_padded_start / _end;
+ *   out_region_ref_hap  the output haplotype, counted inside the region, that trim_to leaves as ref_haplotype (the last with
+ *                is_ref in the map's order), -1 without one
+ * per input haplotype [n_haps]: hap_fate  the rank it got inside its region (>= 0), or PHMM_TRIM_FATE_DUPLICATE with hap_dup_of =
+ *   its class's representative (counted inside the region; UINT32_MAX otherwise), _CUT_IN_DELETION, _EMPTY, _ALL_INSERTION, or
+ *   _NOT_TRIMMED (its region has no variation or a negative status)
+ * the trimmed haplotypes, dense, regions in order, inside a region in the BTreeMap's order: out_region_hap_off [n_regions+1],
+ *   out_hap_off, out_hap_cigar_off [n_out+1], out_hap_bases, out_hap_cigar, out_hap_start_wrt_ref, out_hap_is_ref [n_out],
+ *   out_hap_source [n_out] the input haplotype, counted inside the region.  They pass as they are into phmm_region_compute and
+ *   phmm_discover_events; the reference bases and region_ref_start stay the input's (trim_to does not touch
+ *   full_reference_with_padding).  Nothing is larger than the input: size the per-haplotype arrays for n_haps (+1 for offsets),
+ *   out_hap_bases as hap_bases, out_hap_cigar as hap_cigar; entries behind n_out = out_region_hap_off[n_regions] are not written.
+ * Limits as phmm_discover_events: PHMM_EVENTS_MAX_REF reference bases and PHMM_EVENTS_MAX_HAPS haplotypes per region; haplotype
+ * bases + CIGAR elements + 8 per haplotype below 2^31.  The device workspace is the one phmm_discover_events keeps.
+ * The result is the same from run to run and whatever else is in the batch: no atomics, one writer per element.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): a required array NULL; offsets that do not
+ * start at 0 or are not monotonic; a region above a limit; a position beyond 2^62; an active span that is empty or not inside
+ * the padded span; a haplotype location that ends before it starts; hap_start_wrt_ref + the location's length beyond 32 bits;
+ * a base outside the reference's allele alphabet; a CIGAR element with an unknown operator or length 0.  n_regions == 0 and
+ * regions without haplotypes are fine.  One thread per handle.
+ */
+#define PHMM_TRIM_VARIATION_SPAN 1u
+#define PHMM_TRIM_VARIATION_SET 2u
+#define PHMM_TRIM_FATE_DUPLICATE (-1)
+#define PHMM_TRIM_FATE_CUT_IN_DELETION (-2)
+#define PHMM_TRIM_FATE_EMPTY (-3)
+#define PHMM_TRIM_FATE_ALL_INSERTION (-4)
+#define PHMM_TRIM_FATE_NOT_TRIMMED (-5)
+#define PHMM_TRIM_STATUS_LOCATION (-16)
+#define PHMM_TRIM_STATUS_LENGTH (-17)
+#define PHMM_TRIM_STATUS_OPERATOR (-18)
+#define PHMM_TRIM_STATUS_NOT_FOUND (-19)
+#define PHMM_TRIM_STATUS_BUILDER (-20)
+#define PHMM_TRIM_STATUS_REF_ELIMINATED (-21)
+#define PHMM_TRIM_STATUS_REPEAT_SLICE (-22)
+int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
+                      const uint64_t *region_ref_start, const uint64_t *region_active_start, const uint64_t *region_active_end,
+                      const uint64_t *region_padded_start, const uint64_t *region_padded_end, const uint32_t *region_hap_off,
+                      const uint32_t *hap_off, const uint8_t *hap_bases, const uint32_t *hap_cigar_off, const uint32_t *hap_cigar,
+                      const uint32_t *hap_start_wrt_ref, const uint64_t *hap_loc_start, const uint64_t *hap_loc_end,
+                      const uint8_t *hap_is_ref, uint32_t max_mnp_distance, const uint32_t *padding, int32_t *region_status,
+                      uint8_t *variation_present, uint64_t *variant_start, uint64_t *variant_end, uint64_t *padded_start,
+                      uint64_t *padded_end, uint64_t *new_active_start, uint64_t *new_active_end, uint64_t *new_padded_start,
+                      uint64_t *new_padded_end, int32_t *hap_fate, uint32_t *hap_dup_of, uint32_t *out_region_hap_off,
+                      uint32_t *out_hap_off, uint8_t *out_hap_bases, uint32_t *out_hap_cigar_off, uint32_t *out_hap_cigar,
+                      uint32_t *out_hap_start_wrt_ref, uint32_t *out_hap_source, uint8_t *out_hap_is_ref,
+                      int32_t *out_region_ref_hap);
+
+/*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).
  * The PHMM_* environment variables of the same names (upper case) are read once, by phmm_create; phmm_set_switch changes one
  * switch of one handle afterwards.  What is left of them after round 6 (every switch whose A/B was closed went with its code):

@@ -1315,3 +1315,170 @@ pub fn assembly_kmers(
         })
         .collect()
 }
+
+/// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
+/// location (closed) and whether it is the reference haplotype.
+pub struct TrimHaplotype<'a> {
+    pub bases: &'a [u8],
+    pub cigar: &'a [rust_htslib::bam::record::Cigar],
+    pub start_wrt_ref: usize,
+    pub loc: (usize, usize),
+    pub is_ref: bool,
+}
+
+/// One region for `trim_regions`: `full_reference_with_padding` and where it starts, the active span and the padded span (closed),
+/// the haplotypes in the set's insertion order.
+pub struct TrimRegion<'a> {
+    pub reference: &'a [u8],
+    pub ref_start: usize,
+    pub active: (usize, usize),
+    pub padded: (usize, usize),
+    pub haplotypes: Vec<TrimHaplotype<'a>>,
+}
+
+/// A trimmed haplotype as `trim_to` leaves it; `source` is its index among the region's input haplotypes.
+pub struct TrimmedHaplotype {
+    pub bases: Vec<u8>,
+    pub cigar: rust_htslib::bam::record::CigarString,
+    pub start_wrt_ref: usize,
+    pub is_ref: bool,
+    pub source: usize,
+}
+
+/// What `trim_regions` returns for one region.  `status` < 0: the reference returns the empty model (`PHMM_EV_STATUS_*`) or
+/// panics (`PHMM_TRIM_STATUS_*`) there.  `span_variation` is the trimmer's `is_variation_present`, `set_variation` the result
+/// set's `variation_present` after `trim_to`; `fates[i]` is the rank of input haplotype i or a `PHMM_TRIM_FATE_*`.
+pub struct TrimmedRegion {
+    pub status: i32,
+    pub span_variation: bool,
+    pub set_variation: bool,
+    pub variant_span: (usize, usize),
+    pub padded_span: (usize, usize),
+    pub new_active: (usize, usize),
+    pub new_padded: (usize, usize),
+    pub fates: Vec<i32>,
+    pub dup_of: Vec<Option<usize>>,
+    pub haplotypes: Vec<TrimmedHaplotype>,
+    pub ref_haplotype: Option<usize>,
+}
+
+/// `get_variation_events`, `AssemblyRegionTrimmer::trim` (legacy trimming off) and `AssemblyResultSet::trim_to` of
+/// `call_region` (haplotype_caller_engine.rs:1194-1243) for a batch of regions.  `padding`: SNP, indel and STR padding and
+/// `max_extension_into_region_padding` in THIS order (`AssemblyRegionTrimmer::new` takes the indel padding first).
+pub fn trim_regions(regions: &[TrimRegion], max_mnp_distance: usize, padding: [usize; 4]) -> Vec<TrimmedRegion> {
+    let n_regions = regions.len();
+    let (mut region_ref_off, mut region_hap_off, mut hap_off, mut hap_cigar_off) = (vec![0u32], vec![0u32], vec![0u32], vec![0u32]);
+    let (mut ref_bases, mut hap_bases, mut hap_cigar) = (Vec::<u8>::new(), Vec::<u8>::new(), Vec::<u32>::new());
+    let (mut ref_start, mut active_start, mut active_end) = (Vec::<u64>::new(), Vec::<u64>::new(), Vec::<u64>::new());
+    let (mut padded_start, mut padded_end) = (Vec::<u64>::new(), Vec::<u64>::new());
+    let (mut hap_start, mut loc_start, mut loc_end, mut is_ref) = (Vec::<u32>::new(), Vec::<u64>::new(), Vec::<u64>::new(), Vec::<u8>::new());
+    for g in regions {
+        ref_bases.extend_from_slice(g.reference);
+        region_ref_off.push(ref_bases.len() as u32);
+        ref_start.push(g.ref_start as u64);
+        active_start.push(g.active.0 as u64);
+        active_end.push(g.active.1 as u64);
+        padded_start.push(g.padded.0 as u64);
+        padded_end.push(g.padded.1 as u64);
+        for hap in g.haplotypes.iter() {
+            hap_bases.extend_from_slice(hap.bases);
+            hap_off.push(hap_bases.len() as u32);
+            hap_cigar.extend_from_slice(&encode_cigar(hap.cigar));
+            hap_cigar_off.push(hap_cigar.len() as u32);
+            hap_start.push(hap.start_wrt_ref as u32);
+            loc_start.push(hap.loc.0 as u64);
+            loc_end.push(hap.loc.1 as u64);
+            is_ref.push(hap.is_ref as u8);
+        }
+        region_hap_off.push(hap_start.len() as u32);
+    }
+    let n_haps = hap_start.len();
+    let pad: Vec<u32> = padding.iter().map(|&p| p as u32).collect();
+    let mut status = vec![0i32; n_regions];
+    let mut variation = vec![0u8; n_regions];
+    let mut spans = vec![vec![0u64; n_regions]; 8];
+    let (mut fate, mut dup_of) = (vec![0i32; n_haps], vec![0u32; n_haps]);
+    let (mut out_region_hap_off, mut out_hap_off, mut out_cigar_off) = (vec![0u32; n_regions + 1], vec![0u32; n_haps + 1], vec![0u32; n_haps + 1]);
+    let (mut out_bases, mut out_cigar) = (vec![0u8; hap_bases.len()], vec![0u32; hap_cigar.len()]);
+    let (mut out_start, mut out_source, mut out_is_ref) = (vec![0u32; n_haps], vec![0u32; n_haps], vec![0u8; n_haps]);
+    let mut ref_hap = vec![0i32; n_regions];
+    let span_ptr: Vec<*mut u64> = spans.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_trim_regions(
+                h,
+                n_regions as u32,
+                region_ref_off.as_ptr(),
+                ref_bases.as_ptr(),
+                ref_start.as_ptr(),
+                active_start.as_ptr(),
+                active_end.as_ptr(),
+                padded_start.as_ptr(),
+                padded_end.as_ptr(),
+                region_hap_off.as_ptr(),
+                hap_off.as_ptr(),
+                hap_bases.as_ptr(),
+                hap_cigar_off.as_ptr(),
+                hap_cigar.as_ptr(),
+                hap_start.as_ptr(),
+                loc_start.as_ptr(),
+                loc_end.as_ptr(),
+                is_ref.as_ptr(),
+                max_mnp_distance as u32,
+                pad.as_ptr(),
+                status.as_mut_ptr(),
+                variation.as_mut_ptr(),
+                span_ptr[0],
+                span_ptr[1],
+                span_ptr[2],
+                span_ptr[3],
+                span_ptr[4],
+                span_ptr[5],
+                span_ptr[6],
+                span_ptr[7],
+                fate.as_mut_ptr(),
+                dup_of.as_mut_ptr(),
+                out_region_hap_off.as_mut_ptr(),
+                out_hap_off.as_mut_ptr(),
+                out_bases.as_mut_ptr(),
+                out_cigar_off.as_mut_ptr(),
+                out_cigar.as_mut_ptr(),
+                out_start.as_mut_ptr(),
+                out_source.as_mut_ptr(),
+                out_is_ref.as_mut_ptr(),
+                ref_hap.as_mut_ptr(),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP trim_regions failed ({}): {}", rc, last_error(h));
+        }
+    });
+    let pair = |k: usize, g: usize| (spans[k][g] as usize, spans[k + 1][g] as usize);
+    (0..n_regions)
+        .map(|g| {
+            let haps = region_hap_off[g] as usize..region_hap_off[g + 1] as usize;
+            let outs = out_region_hap_off[g] as usize..out_region_hap_off[g + 1] as usize;
+            TrimmedRegion {
+                status: status[g],
+                span_variation: variation[g] as u32 & PHMM_TRIM_VARIATION_SPAN != 0,
+                set_variation: variation[g] as u32 & PHMM_TRIM_VARIATION_SET != 0,
+                variant_span: pair(0, g),
+                padded_span: pair(2, g),
+                new_active: pair(4, g),
+                new_padded: pair(6, g),
+                fates: fate[haps.clone()].to_vec(),
+                dup_of: dup_of[haps].iter().map(|&d| if d == u32::MAX { None } else { Some(d as usize) }).collect(),
+                haplotypes: outs
+                    .map(|k| TrimmedHaplotype {
+                        bases: out_bases[out_hap_off[k] as usize..out_hap_off[k + 1] as usize].to_vec(),
+                        cigar: decode_cigar(&out_cigar[out_cigar_off[k] as usize..out_cigar_off[k + 1] as usize]),
+                        start_wrt_ref: out_start[k] as usize,
+                        is_ref: out_is_ref[k] != 0,
+                        source: out_source[k] as usize,
+                    })
+                    .collect(),
+                ref_haplotype: if ref_hap[g] < 0 { None } else { Some(ref_hap[g] as usize) },
+            }
+        })
+        .collect()
+}

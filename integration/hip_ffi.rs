@@ -143,6 +143,22 @@ pub const PHMM_ASM_KMER_NON_UNIQUE: c_uint = 1;
 pub const PHMM_ASM_KMER_THREADED: c_uint = 2;
 pub const PHMM_ASM_KMER_THREAD_START: c_uint = 4;
 pub const PHMM_ASM_KMER_FIRST: c_uint = 8;
+/// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
+/// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
+pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
+pub const PHMM_TRIM_VARIATION_SET: c_uint = 2;
+pub const PHMM_TRIM_FATE_DUPLICATE: c_int = -1;
+pub const PHMM_TRIM_FATE_CUT_IN_DELETION: c_int = -2;
+pub const PHMM_TRIM_FATE_EMPTY: c_int = -3;
+pub const PHMM_TRIM_FATE_ALL_INSERTION: c_int = -4;
+pub const PHMM_TRIM_FATE_NOT_TRIMMED: c_int = -5;
+pub const PHMM_TRIM_STATUS_LOCATION: c_int = -16;
+pub const PHMM_TRIM_STATUS_LENGTH: c_int = -17;
+pub const PHMM_TRIM_STATUS_OPERATOR: c_int = -18;
+pub const PHMM_TRIM_STATUS_NOT_FOUND: c_int = -19;
+pub const PHMM_TRIM_STATUS_BUILDER: c_int = -20;
+pub const PHMM_TRIM_STATUS_REF_ELIMINATED: c_int = -21;
+pub const PHMM_TRIM_STATUS_REPEAT_SLICE: c_int = -22;
 
 /// `phmm_finalize_config`: which steps of `finalize_regions` run, and their parameters
 #[repr(C)]
@@ -952,12 +968,58 @@ extern "C" {
         ref_kmer_id: *mut u32,
         read_kmer_id: *mut u32,
     ) -> c_int;
+    /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
+    /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;
+    /// `padding`: SNP, indel, STR padding and max_extension_into_region_padding
+    pub fn phmm_trim_regions(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_ref_start: *const u64,
+        region_active_start: *const u64,
+        region_active_end: *const u64,
+        region_padded_start: *const u64,
+        region_padded_end: *const u64,
+        region_hap_off: *const u32,
+        hap_off: *const u32,
+        hap_bases: *const u8,
+        hap_cigar_off: *const u32,
+        hap_cigar: *const u32,
+        hap_start_wrt_ref: *const u32,
+        hap_loc_start: *const u64,
+        hap_loc_end: *const u64,
+        hap_is_ref: *const u8,
+        max_mnp_distance: u32,
+        padding: *const u32,
+        region_status: *mut i32,
+        variation_present: *mut u8,
+        variant_start: *mut u64,
+        variant_end: *mut u64,
+        padded_start: *mut u64,
+        padded_end: *mut u64,
+        new_active_start: *mut u64,
+        new_active_end: *mut u64,
+        new_padded_start: *mut u64,
+        new_padded_end: *mut u64,
+        hap_fate: *mut i32,
+        hap_dup_of: *mut u32,
+        out_region_hap_off: *mut u32,
+        out_hap_off: *mut u32,
+        out_hap_bases: *mut u8,
+        out_hap_cigar_off: *mut u32,
+        out_hap_cigar: *mut u32,
+        out_hap_start_wrt_ref: *mut u32,
+        out_hap_source: *mut u32,
+        out_hap_is_ref: *mut u8,
+        out_region_ref_hap: *mut i32,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash> trim=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

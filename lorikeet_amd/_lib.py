@@ -180,6 +180,10 @@ SYMBOLS = [
                                    C.POINTER(C.c_int64), u32p, u32p, u8p, C.POINTER(C.c_int32)]),
     ("phmm_assembly_kmers", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
                                       u32p, u32p, u32p, u32p, u32p, u8p, u8p, u32p, u32p]),
+    ("phmm_trim_regions", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
+                                    u64p, u64p, u8p, C.c_uint32, u32p, C.POINTER(C.c_int32), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
+                                    u64p, u64p, C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u32p, u32p, u32p, u32p, u8p,
+                                    C.POINTER(C.c_int32)]),
     ("phmm_set_switch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("phmm_get_stat", C.c_uint64, [C.c_void_p, C.c_char_p]),
     ("phmm_build_info", C.c_char_p, []),

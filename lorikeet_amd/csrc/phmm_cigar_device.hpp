@@ -140,6 +140,27 @@ __device__ int trim_by_bases(Builder &T, const uint32_t *src, uint32_t n, uint64
     return st;
 }
 
+// trim_cigar(cigar, start, end, by_reference = true).make_and_record_deletions_removed_result() (alignment_utils.rs:334-386,
+// :853): the same loop measured on the reference.  An insertion that sits exactly at `start` or at `end + 1` has no length
+// there and stays, with its whole length (:361-373).
+__device__ int trim_by_reference(Builder &T, const uint32_t *src, uint32_t n, uint64_t start, uint64_t end, uint32_t *leading, uint32_t *trailing) {
+    if (end < start) return CIGAR_ERR_PANIC;  // "End position cannot be before start position"
+    uint64_t e_start, e_end = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        e_start = e_end;
+        e_end = e_start + ref_len_of(src[i]);
+        if (e_end < start || (e_end == start && e_start < start)) continue;
+        if (e_start > end && e_end > end + 1) break;
+        const uint64_t overlap = e_end == e_start ? (uint64_t)len_of(src[i]) : (end + 1 < e_end ? end + 1 : e_end) - (start > e_start ? start : e_start);
+        const int st = T.add(elem(op_of(src[i]), (uint32_t)overlap));
+        if (st != CIGAR_OK) return st;
+    }
+    if (e_end < end) return CIGAR_ERR_PANIC;  // "Cigar elements don't reach end position (inclusive)"
+    const int st = T.make(trailing);
+    if (st == CIGAR_OK && leading) *leading = T.leading_removed;
+    return st;
+}
+
 // left_align_indels(cigar, ref, read, read_start) (alignment_utils.rs:425-566, normalize_alleles :585-640) into T;
 // `rtl` holds result_right_to_left.  The source may be T's own storage's neighbour, never T itself.
 __device__ int left_align(Builder &T, uint32_t *t_storage, uint32_t capacity, uint32_t *rtl, const uint32_t *src, uint32_t n,

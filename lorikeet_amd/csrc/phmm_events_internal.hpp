@@ -62,5 +62,6 @@ struct EventsParams {
 };
 
 hipError_t launch_events(const EventsParams &p, hipStream_t stream);
+hipError_t launch_event_maps(const EventsParams &p, hipStream_t stream);  // the haplotypes' event maps alone, into the workspace
 
 }  // namespace phmm

@@ -592,4 +592,11 @@ hipError_t launch_events(const EventsParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// events_hap_kernel alone (phmm_trim_regions): every haplotype's event map into the workspace -- ws_ev / ws_alt by ws_ev_off,
+// hap_n_ev, hap_n_alt, hap_status -- and nothing else of EventsParams is read or written.
+hipError_t launch_event_maps(const EventsParams &p, hipStream_t stream) {
+    if (p.n_haps) events_hap_kernel<<<p.n_haps, 64, 0, stream>>>(p);
+    return hipGetLastError();
+}
+
 }  // namespace phmm

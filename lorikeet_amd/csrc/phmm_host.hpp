@@ -158,8 +158,8 @@ struct phmm_handle {
         std::unordered_map<uint64_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> tables;
     } gwork;
     // grow-only staging of phmm_allele_frequency (phmm_af.cpp), phmm_annotate_events (phmm_annotate.cpp), phmm_assign_genotypes (phmm_assign.cpp)
-    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging, asm_staging;
-    // phmm_discover_events' device-only workspace (phmm_events.cpp): grow-only, no host mirror
+    StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging, asm_staging, trim_staging;
+    // phmm_discover_events' device-only workspace (phmm_events.cpp), which phmm_trim_regions (phmm_trim.cpp) shares: grow-only, no host mirror
     char *events_scratch = nullptr;
     size_t events_scratch_cap = 0;
     char *activity_scratch = nullptr;  // phmm_activity_profile: the reads' slots and position tables, the event list, device only
