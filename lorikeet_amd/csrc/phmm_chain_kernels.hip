@@ -67,6 +67,35 @@ __device__ __forceinline__ double from_left_inject(double v, double inject, bool
     return __hiloint2double(hi, lo);
 }
 
+// make_row_bytes' pre-scaled record for the row producer, where a wave waits alone for every look-up: the eight look-ups
+// depend on the bytes alone, so all of them are made first -- one wait, not one per divergent block -- and `first`, `last`
+// and a read 'N' select afterwards (an ignored byte may be any byte: every table has 256 entries).  The arithmetic is
+// make_row_bytes', expression by expression: the records are equal bit for bit.  (make_row_bytes keeps its conditional
+// look-ups: unconditional ones cost its other users registers, and the general path below scratch.)
+__device__ __forceinline__ RowConst row_bytes_one_go(const ForwardParams &p, uint32_t x, uint32_t q, uint32_t q_prev, uint32_t iq,
+                                                     uint32_t dq, uint32_t dq_prev, uint32_t g, uint32_t g_next, bool first,
+                                                     bool last) {
+    const uint32_t mx = max(iq, dq), mn = min(iq, dq);
+    const double mi = p.eps[iq], ii = p.eps[g], mm = p.mm[((mx * (mx + 1)) >> 1) + mn];
+    const double e_g_next = p.eps[g_next], e_q_prev = p.eps[q_prev], e_dq_prev = p.eps[dq_prev];
+    const double inv_om = p.inv_om[g], ratio_mis = p.ratio_mis[q];
+    RowConst n;
+    n.dd = ii;
+    const double im = 1.0 - ii;
+    const double im_next = last ? 1.0 : 1.0 - e_g_next;
+    const double pm_prev = first ? 1.0 : 1.0 - e_q_prev;
+    n.mm = mm * pm_prev;
+    n.bI = mi * im_next * pm_prev;
+    n.gI = ii * (im_next * inv_om);
+    n.dDp = first ? 1.0 : e_dq_prev * im * pm_prev;  // dD(i-1) = md(i-1) * im(i)
+    n.pm = 1.0;
+    n.px = (x == 'N') ? 1.0 : ratio_mis;             // read 'N' matches everything (pair_hmm.rs:643)
+    n.x = x;
+    n.pad0 = 0;
+    n.pad1 = 0.0;
+    return n;
+}
+
 template <int K>
 __device__ __forceinline__ void chain_fallback(const ForwardParams &p, const ChainItem &it, RowConst *ring, int lane,
                                                int grp, int l, const HapCols<K> &hc, int H, bool hv, int a, int Nh) {
@@ -190,8 +219,7 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
     const uint32_t rb = it.read_begin;
     const uint32_t byte0 = p.read_off[rb];
     const uint32_t bytes = p.read_off[it.read_end] - byte0;
-    bool z = false;
-    for (uint32_t i = lane; i < bytes; i += WAVE) z |= row_blocks_prescale(p, byte0 + i);
+    const bool z = chain_blocks_prescale(p, byte0, bytes, lane);
     if ((__ballot(z) | __ballot(lane_n)) != 0ull) {  // rare: exact but unchained
         if constexpr (MODE == CHAIN_SUFFIX) {
             // (a suffix cannot be swept alone the general way: its pairs are left to the exact pass -- NaN asks for it)
@@ -232,9 +260,15 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
     const double c_unit = ldexp(1.0, 1010);  // common D(0,j) of every haplotype, see the header
 
     // ---- row producer: stream positions [P0, P0 + 64) -> ring ----------------------------------------
-    // Two-phase producer, one ring row per lane: `issue` starts the (cold) loads of a row's quality bytes, `finish`
-    // -- one tick = 64 steps later, when they have long arrived -- looks the (hot, L1/L2-resident) table values
-    // up, builds the record and writes it to the ring.  Only the six bytes live in registers in between.
+    // Two-phase producer, one ring row per lane: `issue` starts the (cold) loads of a row's eight quality bytes and does
+    // nothing else with them, `finish` -- one tick = 64 steps later, when they have long arrived -- looks the (hot, L1/L2-
+    // resident) table values up, builds the record and writes it to the ring.  Only the eight bytes live in registers in
+    // between.  In the compiled kernel: eight global_load_ubyte on every lane, no s_waitcnt vmcnt from there through the
+    // sweep loop (the emit blocks, once per read, wait for their own two loads), and in finish() one wait for the bytes,
+    // the eight look-ups together, and waits counting down as the values are used: one table latency per tick.  (Loads
+    // under `if (producer && ...)` came out as exec-masked loads whose results were merged into the pending registers at
+    // once -- a wait for every load right behind issue(), before the sweep -- and look-ups inside the row-kind branches
+    // as one divergent block and one vmcnt(0) each.)
     uint32_t pb_x = 0, pb_q = 0, pb_qp = 0, pb_i = 0, pb_d = 0, pb_dp = 0, pb_g = 0, pb_gn = 0;
     double pb_bM = 0.0, pb_bD = 0.0;  // CHAIN_SUFFIX: the parked column's M~, D' of the row in the making
     int p_Q = 0;
@@ -270,33 +304,57 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
                 pb_bD = at[1];
             }
         }
-        if (producer && p_lo < pn && row >= 0 && row <= R) {
-            pb_qp = row > 0 ? (uint32_t)p.base_q[ro + row - 1] : 0u;  // row == R: the SUM row needs pm(R)
-            if (row < R) {
-                pb_x = p.read_bases[ro + row];
-                pb_q = p.base_q[ro + row];
-                pb_i = p.ins_q[ro + row];
-                pb_d = p.del_q[ro + row];
-                pb_dp = row > 0 ? (uint32_t)p.del_q[ro + row - 1] : 0u;
-                pb_g = p.gcp[ro + row];
-                pb_gn = row + 1 < R ? (uint32_t)p.gcp[ro + row + 1] : 0u;
-            }
-        }
+        // Eight byte loads, all of them on every lane and none looked at before finish(): a lane without a row (lead-in,
+        // past its stream's last read) reads the chain's first byte, and a row's missing neighbour (row 0 has no row before
+        // it, the last row none after it, SUM and RESET rows no byte of their own) is clamped into the read -- finish()
+        // selects by the row kind.  A SUM row needs pm(R) (pb_qp: the last row's quality), a RESET row the first gcp of the
+        // next read (in pb_g, which it does not use otherwise); that read follows this one in the arrays.
+        const bool live = producer && p_lo < pn && row >= 0 && R > 0;
+        const uint32_t at = live ? ro + (uint32_t)min(row, R - 1) : byte0;
+        const uint32_t at_prev = live ? ro + (uint32_t)max(min(row, R) - 1, 0) : byte0;
+        const uint32_t at_next = live ? ro + (uint32_t)min(row + 1, R - 1) : byte0;
+        const uint32_t at_g = (live && row > R && p_lo + 1 < pn) ? ro + (uint32_t)R : at;
+        pb_x = p.read_bases[at];
+        pb_q = p.base_q[at];
+        pb_i = p.ins_q[at];
+        pb_d = p.del_q[at];
+        pb_g = p.gcp[at_g];
+        pb_qp = p.base_q[at_prev];
+        pb_dp = p.del_q[at_prev];
+        pb_gn = p.gcp[at_next];
     };
     auto finish = [&](int Q0) {  // the issued position = ring positions [Q0, Q0 + TPS) of every stream
         const int Q = Q0 + pj;     // stream position = ring position - LEAD
         const int lo = p_lo, row = p_row, R = p_R;
+        // Every table value of every row kind depends on the pending bytes alone, so all of them are looked up first,
+        // whatever the lane's row is (one wait for the bytes, one for the values), and the row kind selects afterwards.  The
+        // other kinds' values are among a plain row's: pm(R) of a SUM row (pb_qp holds the last row's quality) and, for a
+        // RESET row, eps of the next read's first gcp (in pb_g: the record's dd).
+        // (K = 22 ... 25 sit at the 256-register limit and have none to hold eight values at once: they look a value up
+        // where its row kind uses it, which is what every K did before.)
+        constexpr bool ONE_GO = K <= 21;
+        RowConst plain;
+        double pm_last = 0.0;
+        if constexpr (ONE_GO) {
+            plain = row_bytes_one_go(p, pb_x, pb_q, pb_qp, pb_i, pb_d, pb_dp, pb_g, pb_gn, row == 0, row + 1 >= R);
+            pm_last = 1.0 - p.eps[pb_qp];
+        }
         RowConst n;
         if (lo < pn && row >= 0) {
             if (row < R) {
-                n = make_row_bytes(p, pb_x, pb_q, pb_qp, pb_i, pb_d, pb_dp, pb_g, pb_gn, row == 0, row + 1 >= R, true);
+                if constexpr (ONE_GO) n = plain;
+                else n = make_row_bytes(p, pb_x, pb_q, pb_qp, pb_i, pb_d, pb_dp, pb_g, pb_gn, row == 0, row + 1 >= R, true);
             } else if (row == R) {  // SUM row: M_S(k) = M(R,k-1) + I(R,k-1), I_S(k) = M(R,k) + I(R,k); pad0 = read index in the chain
-                n.mm = 1.0 - p.eps[pb_qp]; n.bI = n.mm; n.gI = 1.0; n.dDp = 0.0; n.dd = 1.0; n.pm = 1.0; n.px = 1.0;
+                if constexpr (!ONE_GO) pm_last = 1.0 - p.eps[pb_qp];
+                n.mm = pm_last; n.bI = n.mm; n.gI = 1.0; n.dDp = 0.0; n.dd = 1.0; n.pm = 1.0; n.px = 1.0;
                 n.x = X_PAD; n.pad0 = (uint32_t)lo; n.pad1 = 0.0;
             } else {                // RESET row; pad1 = D'(0,.) of the next read = 2^1010 * im of its first row
                 n.mm = 0.0; n.bI = 0.0; n.gI = 0.0; n.dDp = 0.0; n.dd = 1.0; n.pm = 0.0; n.px = 0.0;
                 n.x = X_NONE; n.pad0 = 0;
-                n.pad1 = c_unit * (lo + 1 < pn ? 1.0 - p.eps[p.gcp[roff[pcb + lo + 1]]] : 1.0);
+                double e_first;
+                if constexpr (ONE_GO) e_first = plain.dd;
+                else e_first = p.eps[pb_g];
+                n.pad1 = c_unit * (lo + 1 < pn ? 1.0 - e_first : 1.0);
             }
             if constexpr (MODE == CHAIN_SUFFIX) {  // the left neighbour of the item's first lanes in this row (pm is not read by the sweep)
                 n.pm = pb_bM;
@@ -311,6 +369,9 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
             if ((Q & NM) == 0) ring[slot + NM + 1] = n;  // the stream's guard slot
         }
     };
+    // planner guarantees every read has >= 1 base; a stream without reads only ever sees neutral rows
+    // (looked up here, among the cold waits of the first ticks: behind the last issue() it would drain that one's loads)
+    const double c0 = c_unit * (n_mine > 0 ? 1.0 - p.eps[p.gcp[roff[sid * (n_sub + 1)]]] : 1.0);
     issue();
     finish(0);
     issue();
@@ -321,8 +382,6 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
     issue();
 
     // ---- state ---------------------------------------------------------------------------------------
-    // planner guarantees every read has >= 1 base; a stream without reads only ever sees neutral rows
-    const double c0 = c_unit * (n_mine > 0 ? 1.0 - p.eps[p.gcp[roff[sid * (n_sub + 1)]]] : 1.0);
     double Mp[K], Ip[K], Dp[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -374,8 +433,9 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
         const int b = __popc(park_mask & ((1u << l) - 1u));
         park_at = reinterpret_cast<double2 *>(park) + ((size_t)x->park_row0 + (size_t)b * park_rows + (size_t)q);
     }
-    // Outer loop = one producer tick (TPS steps), inner loop = the sweep.  The producer's pending bytes are
-    // defined before the inner loop and first used after it, so their loads have a tick to land.
+    // Outer loop = one producer tick (TPS steps), inner loop = the sweep.  The producer's pending bytes are loaded
+    // before the inner loop, unconditionally and straight into their registers, and first read after it, so their loads
+    // have a tick to land (the loads of the issue() in front of the loop, once per wave, are still waited for there).
     // The first tick is shortened by a per-block even phase (the ring only gets further ahead), so that the two
     // waves sharing a SIMD do not run their producers -- the one latency-exposed part -- at the same time.
     const int phase = (int)((blockIdx.x * 2654435761u) >> 26) & (TPS - 2);
