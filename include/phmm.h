@@ -947,8 +947,9 @@ int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
  *   filter_size [1]; profile_len [profiles]; profile_prob (float) [P + profiles * max_filter_size]: the profiles of all windows
  *                  in order (ceil(window_len / profile_size) per window), profile k's list from P_k + k * max_filter_size, P_k
  *                  the global index of its first position; profile_len[k] entries of it are the state list, the rest is 0
- * Out of scope, the caller's: BAM reading and read_is_filtered, limiting_interval, pop_ready_assembly_regions and below, the
- * depth runs for ANI (they read ref_depth + non_ref_depth).
+ * Out of scope, the caller's: BAM reading and read_is_filtered, limiting_interval, the depth runs for ANI (they read ref_depth +
+ * non_ref_depth).  pop_ready_assembly_regions and the regions' reads are phmm_assembly_regions, which takes profile_prob,
+ * profile_len and the read arrays of this call as they are.
  * Footprint: staging for the inputs and the wanted outputs; on the device alone, kept by the handle until phmm_destroy, 6 bytes
  * per pileup slot and about 130 bytes per position plus the outputs not asked for.
  * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): ploidy 0 or above the maximum, no samples,
@@ -1354,6 +1355,85 @@ int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint32_t *region
                       uint32_t *out_hap_off, uint8_t *out_hap_bases, uint32_t *out_hap_cigar_off, uint32_t *out_hap_cigar,
                       uint32_t *out_hap_start_wrt_ref, uint32_t *out_hap_source, uint8_t *out_hap_is_ref,
                       int32_t *out_region_ref_hap);
+
+/*
+ * phmm_assembly_regions -- the band-passed state lists of phmm_activity_profile cut into assembly regions, and the staged reads
+ * each region's fetch returns, for many profiles in ONE call.  P = src/activity_profile/activity_profile.rs, A =
+ * src/assembly/assembly_region.rs, T = src/assembly/assembly_region_iterator.rs, U = src/utils/interval_utils.rs; a profile is
+ * made and handed over at src/haplotype/haplotype_caller_engine.rs:947, :982-1136, and popped at
+ * src/assembly/assembly_region_walker.rs:124-131.
+ * Part A, per profile: pop_ready_assembly_regions (P:371-412) as written, every quirk kept:
+ *   force        computed per iteration, the argument ignored (P:384-392): false for the first region, afterwards `the region
+ *                before's active start != stop + 1`, stop = region_stop_loc, the position of the last state that was ADDED
+ *                (profile_stop), not the end of the band-passed list, which runs up to F states further.  So a list shorter
+ *                than max_region_size + max_prob_propagation yields no region at all (P:552-558), and after a region that
+ *                happens to start at stop + 1 the next one is unforced and the tail may stay unpopped
+ *   boundary     find_first_activity_boundary (P:621-640): `prob > threshold` in f32, a NaN is inactive; bounded by the remaining
+ *                states and by max_region_size
+ *   cut site     find_best_cut_site (P:582-605) only for an active run that reaches exactly max_region_size: downward from
+ *                end - 1 to min_region_size with `cur < min_p && is_minimum(i)`, min_p from f32::MAX: the smallest probability
+ *                wins, the HIGHEST index among equals; nothing qualifies: end.  is_minimum (P:660-668) is of the CURRENT list,
+ *                after earlier drains: false at its index 0 and at the last state of the whole list, else
+ *                p[i] <= p[i+1] && p[i] < p[i-1].  The assertion end >= min_region_size (P:583-586) fails only where it is
+ *                reached: PHMM_REG_STATUS_MIN_REGION_SIZE
+ *   region       end = min(start + offset, contig length - 1) (P:495-502); region_states = offset + 1 states are drained, which
+ *                may be more than the span holds; region_density = #{drained states with prob > 0.05} as f32 / span size as f32
+ *                (P:506-508).  A region that would START past contig length - 1 (the list keeps the state AT the contig
+ *                length) underflows SimpleInterval::size there: PHMM_REG_STATUS_START_PAST_CONTIG.  Either status ends the
+ *                profile at that region: the regions before it stand, other profiles are unaffected
+ *   padded span  make_padded_span (A:169-189, U:21-40): saturating start, end min(contig length, end + extension); the None arm
+ *                falls back to the active span
+ *   Inactive regions are returned too (call_region builds the reference model from them).
+ * Part B, skipped when group_read_off is NULL: fill_next_assembly_region_with_reads (T:54-159) without BAM I/O and
+ * read_is_filtered.  Per (region, sample) the staged reads a fetch of [padded start, padded end + 1) returns, in input order: the
+ * rule is htslib's, pos <= padded end && pos + max(reflen, 1) > padded start with reflen over the CIGAR's M, D, N, = and X
+ * elements.  It is htslib's and NOT observable through the reference here: no BAM fixture can be read.  Per read, once:
+ * read_mean_qual = sum(qual as f64) / len as f64, the depth cap's key (T:143-147); a read without qualities gives 0 / 0 = NaN.
+ * Per region its reads over all samples, and PHMM_REG_OVER_DEPTH where they exceed max_input_depth (T:141).
+ * EQUAL to a statement-by-statement restatement, region_density and read_mean_qual bit for bit: each is one correctly rounded
+ * division of exactly representable integers.  The same from run to run and whatever the batch: no atomics, one writer per element.
+ * Inputs: n_profiles; n_windows and n_samples (the groups of the reads; unused without reads); assembly_region_extension,
+ *   min_region_size, max_region_size, max_prob_propagation (the reference's defaults: 100, 50, 300, 50); active_prob_threshold, a
+ *   double that holds an f32 value (0.002); max_input_depth;
+ *   profile_prob (float) [n_prob] with profile_first / profile_len [n_profiles]: phmm_activity_profile's outputs pass as they
+ *   are, profile_first[k] = P_k + k * max_filter_size;  profile_start: the position of state 0;  profile_stop: the position of the
+ *   last added state;  profile_contig_length;  profile_window [n_profiles]: the window whose reads are the profile's;
+ *   group_read_off [n_windows * n_samples + 1], read_pos, read_cigar_off, read_cigar, read_off, read_quals as
+ *   phmm_activity_profile takes them (read_pos must not decrease inside a group)
+ * Outputs: profile_status [n_profiles] 0 or PHMM_REG_STATUS_*; profile_region_off [n_profiles+1];
+ *   per region: region_start / _end, region_padded_start / _end (closed), region_states, region_flags (PHMM_REG_ACTIVE,
+ *   PHMM_REG_FORCED: popped under force, PHMM_REG_OVER_DEPTH), region_density (float), region_n_reads;
+ *   region_read_off [n_regions * n_samples + 1] / region_reads: per (region, sample) at region * n_samples + sample the global
+ *   indices of its reads;  read_mean_qual [n_reads], may be NULL
+ * capacity [2] / required [2] count regions and membership entries, as phmm_discover_events does: when a capacity is too small
+ * the call returns PHMM_ERR_EVENT_CAPACITY with `required` filled and nothing else written; all capacities 0 is the cheap way
+ * to ask, and the per-region and membership arrays may then be NULL.
+ * Out of scope, the caller's: the depth cap's stable sort and take(n) (T:142-150) and the final par_sort_unstable by
+ * BirdToolRead::cmp (T:157) -- they need qnames, flags and mates and apply to few regions; read_is_filtered; the assembly graph.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): min_region_size or max_region_size 0 (the
+ * reference asserts both); a required array NULL; profile_first + profile_len past profile_prob; a contig length of 0; a window
+ * index out of range; offsets that do not start at 0 or are not monotonic; read_pos negative or smaller than that of the read
+ * before it in its group; a CIGAR operator above 8; a position from 2^62 on; reads without samples; states x samples or
+ * windows x samples from 2^31 on.  n_profiles == 0 (required = {0, 0}, the offset arrays hold their 0, nothing else is
+ * written), empty lists and groups without reads are fine.  One thread per handle.
+ */
+#define PHMM_REG_ACTIVE 1u
+#define PHMM_REG_FORCED 2u
+#define PHMM_REG_OVER_DEPTH 4u
+#define PHMM_REG_STATUS_MIN_REGION_SIZE (-1)
+#define PHMM_REG_STATUS_START_PAST_CONTIG (-2)
+int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32_t n_windows, uint32_t n_samples,
+                          uint32_t assembly_region_extension, uint32_t min_region_size, uint32_t max_region_size,
+                          uint32_t max_prob_propagation, double active_prob_threshold, uint32_t max_input_depth, uint32_t n_prob,
+                          const void *profile_prob, const uint32_t *profile_first, const uint32_t *profile_len,
+                          const uint64_t *profile_start, const uint64_t *profile_stop, const uint64_t *profile_contig_length,
+                          const uint32_t *profile_window, const uint32_t *group_read_off, const int64_t *read_pos,
+                          const uint32_t *read_cigar_off, const uint32_t *read_cigar, const uint32_t *read_off,
+                          const uint8_t *read_quals, const uint32_t *capacity, uint32_t *required, int32_t *profile_status,
+                          uint32_t *profile_region_off, uint64_t *region_start, uint64_t *region_end,
+                          uint64_t *region_padded_start, uint64_t *region_padded_end, uint32_t *region_states,
+                          uint32_t *region_flags, void *region_density, uint32_t *region_n_reads, uint32_t *region_read_off,
+                          uint32_t *region_reads, double *read_mean_qual);
 
 /*
  * Developer switches and counters (tests, A/B measurements; never needed in production, NOTEBOOK.md section 11).

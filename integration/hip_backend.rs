@@ -1482,3 +1482,174 @@ pub fn trim_regions(regions: &[TrimRegion], max_mnp_distance: usize, padding: [u
         })
         .collect()
 }
+
+/// One activity profile for `assembly_regions`: its band-passed state list (`is_active_prob` per state), the position of state 0,
+/// the position of the last state that was ADDED (`region_stop_loc`), the contig's length, and the window whose staged reads
+/// are its reads.
+pub struct RegionProfile<'a> {
+    pub probs: &'a [f32],
+    pub start: usize,
+    pub stop: usize,
+    pub contig_length: usize,
+    pub window: usize,
+}
+
+/// The staged reads of `assembly_regions`, as `activity_profile` takes them: per (window, sample) group, window-major, the
+/// reads in fetch order with `pos` not decreasing.
+pub struct RegionReads<'a> {
+    pub n_windows: usize,
+    pub n_samples: usize,
+    pub group_read_off: &'a [u32],
+    pub read_pos: &'a [i64],
+    pub read_cigar_off: &'a [u32],
+    pub read_cigar: &'a [u32],
+    pub read_off: &'a [u32],
+    pub read_quals: &'a [u8],
+}
+
+/// One assembly region as `pop_ready_assembly_regions` returns it (closed spans), with what `fill_next_assembly_region_with_reads`
+/// decides before its sorts: `reads[sample]` are global indices of the staged reads in input order.
+pub struct DeviceAssemblyRegion {
+    pub active_span: (usize, usize),
+    pub padded_span: (usize, usize),
+    pub n_states: usize,
+    pub is_active: bool,
+    pub forced: bool,
+    pub over_depth: bool,
+    pub activity_density: f32,
+    pub reads: Vec<Vec<u32>>,
+}
+
+/// What `assembly_regions` returns: per profile its status (`PHMM_REG_STATUS_*` where the reference panics) and its regions;
+/// per staged read the depth cap's key, `sum(qual as f64) / len as f64`.
+pub struct DeviceAssemblyRegions {
+    pub status: Vec<i32>,
+    pub regions: Vec<Vec<DeviceAssemblyRegion>>,
+    pub read_mean_qual: Vec<f64>,
+}
+
+/// `ActivityProfile::pop_ready_assembly_regions` (activity_profile.rs:371-668) for a batch of profiles and, with `reads`, the
+/// staged reads a fetch of each region's padded span returns (assembly_region_iterator.rs:54-159 without BAM I/O and
+/// `read_is_filtered`).  The depth cap's sort and `take`, and the final sort by `BirdToolRead::cmp`, stay with the caller.
+pub fn assembly_regions(
+    profiles: &[RegionProfile],
+    reads: Option<&RegionReads>,
+    assembly_region_extension: usize,
+    min_region_size: usize,
+    max_region_size: usize,
+    max_prob_propagation: usize,
+    active_prob_threshold: f32,
+    max_input_depth: usize,
+) -> DeviceAssemblyRegions {
+    let n_profiles = profiles.len();
+    let mut prob = Vec::<f32>::new();
+    let (mut first, mut len, mut window) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u32>::new());
+    let (mut start, mut stop, mut contig) = (Vec::<u64>::new(), Vec::<u64>::new(), Vec::<u64>::new());
+    for p in profiles {
+        first.push(prob.len() as u32);
+        len.push(p.probs.len() as u32);
+        prob.extend_from_slice(p.probs);
+        start.push(p.start as u64);
+        stop.push(p.stop as u64);
+        contig.push(p.contig_length as u64);
+        window.push(p.window as u32);
+    }
+    let null32 = std::ptr::null::<u32>();
+    let (n_windows, n_samples, n_reads) = match reads {
+        Some(r) => (r.n_windows, r.n_samples, r.read_pos.len()),
+        None => (0, 0, 0),
+    };
+    // without reads the six arrays are NULL and the call skips part B
+    let (group_read_off, read_pos, read_cigar_off, read_cigar, read_base_off, read_quals) = match reads {
+        Some(r) => (r.group_read_off.as_ptr(), r.read_pos.as_ptr(), r.read_cigar_off.as_ptr(), r.read_cigar.as_ptr(), r.read_off.as_ptr(), r.read_quals.as_ptr()),
+        None => (null32, std::ptr::null::<i64>(), null32, null32, null32, std::ptr::null::<u8>()),
+    };
+    let mut status = vec![0i32; n_profiles];
+    let mut region_off = vec![0u32; n_profiles + 1];
+    let mut mean_qual = vec![0f64; n_reads];
+    let mut required = [0u32; 2];
+    let mut capacity = [0u32; 2];
+    let (mut spans, mut words) = (vec![Vec::<u64>::new(); 4], vec![Vec::<u32>::new(); 3]);
+    let (mut density, mut read_off, mut members) = (Vec::<f32>::new(), Vec::<u32>::new(), Vec::<u32>::new());
+    with_engine(|h| {
+        // the first call asks for the sizes (all capacities 0), the second fills arrays of exactly those sizes
+        for pass in 0..2 {
+            let (r, m) = (capacity[0] as usize, capacity[1] as usize);
+            spans = vec![vec![0u64; r]; 4];
+            words = vec![vec![0u32; r]; 3];
+            density = vec![0f32; r];
+            read_off = vec![0u32; r * n_samples.max(1) + 1];
+            members = vec![0u32; m];
+            let rc = unsafe {
+                phmm_assembly_regions(
+                    h,
+                    n_profiles as u32,
+                    n_windows as u32,
+                    n_samples as u32,
+                    assembly_region_extension as u32,
+                    min_region_size as u32,
+                    max_region_size as u32,
+                    max_prob_propagation as u32,
+                    active_prob_threshold as f64,
+                    max_input_depth.min(u32::MAX as usize) as u32,
+                    prob.len() as u32,
+                    prob.as_ptr() as *const std::os::raw::c_void,
+                    first.as_ptr(),
+                    len.as_ptr(),
+                    start.as_ptr(),
+                    stop.as_ptr(),
+                    contig.as_ptr(),
+                    window.as_ptr(),
+                    group_read_off,
+                    read_pos,
+                    read_cigar_off,
+                    read_cigar,
+                    read_base_off,
+                    read_quals,
+                    capacity.as_ptr(),
+                    required.as_mut_ptr(),
+                    status.as_mut_ptr(),
+                    region_off.as_mut_ptr(),
+                    spans[0].as_mut_ptr(),
+                    spans[1].as_mut_ptr(),
+                    spans[2].as_mut_ptr(),
+                    spans[3].as_mut_ptr(),
+                    words[0].as_mut_ptr(),
+                    words[1].as_mut_ptr(),
+                    density.as_mut_ptr() as *mut std::os::raw::c_void,
+                    words[2].as_mut_ptr(),
+                    read_off.as_mut_ptr(),
+                    members.as_mut_ptr(),
+                    mean_qual.as_mut_ptr(),
+                )
+            };
+            if rc == PHMM_ERR_EVENT_CAPACITY && pass == 0 {
+                capacity = required;
+                continue;
+            }
+            if rc != PHMM_OK {
+                panic!("HIP assembly_regions failed ({}): {}", rc, last_error(h));
+            }
+            break;
+        }
+    });
+    let regions = (0..n_profiles)
+        .map(|k| {
+            (region_off[k] as usize..region_off[k + 1] as usize)
+                .map(|r| DeviceAssemblyRegion {
+                    active_span: (spans[0][r] as usize, spans[1][r] as usize),
+                    padded_span: (spans[2][r] as usize, spans[3][r] as usize),
+                    n_states: words[0][r] as usize,
+                    is_active: words[1][r] & PHMM_REG_ACTIVE != 0,
+                    forced: words[1][r] & PHMM_REG_FORCED != 0,
+                    over_depth: words[1][r] & PHMM_REG_OVER_DEPTH != 0,
+                    activity_density: density[r],
+                    reads: (0..n_samples)   // (0 without reads)
+                        .map(|s| members[read_off[r * n_samples + s] as usize..read_off[r * n_samples + s + 1] as usize].to_vec())
+                        .collect(),
+                })
+                .collect()
+        })
+        .collect();
+    DeviceAssemblyRegions { status, regions, read_mean_qual: mean_qual }
+}

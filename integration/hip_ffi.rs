@@ -159,6 +159,12 @@ pub const PHMM_TRIM_STATUS_NOT_FOUND: c_int = -19;
 pub const PHMM_TRIM_STATUS_BUILDER: c_int = -20;
 pub const PHMM_TRIM_STATUS_REF_ELIMINATED: c_int = -21;
 pub const PHMM_TRIM_STATUS_REPEAT_SLICE: c_int = -22;
+/// `phmm_assembly_regions`: the bits of `region_flags` and the statuses of a profile the reference panics on
+pub const PHMM_REG_ACTIVE: c_uint = 1;
+pub const PHMM_REG_FORCED: c_uint = 2;
+pub const PHMM_REG_OVER_DEPTH: c_uint = 4;
+pub const PHMM_REG_STATUS_MIN_REGION_SIZE: c_int = -1;
+pub const PHMM_REG_STATUS_START_PAST_CONTIG: c_int = -2;
 
 /// `phmm_finalize_config`: which steps of `finalize_regions` run, and their parameters
 #[repr(C)]
@@ -1014,12 +1020,56 @@ extern "C" {
         out_hap_is_ref: *mut u8,
         out_region_ref_hap: *mut i32,
     ) -> c_int;
+    /// pop_ready_assembly_regions over the band-passed lists of phmm_activity_profile (activity_profile.rs:371-668) and, with
+    /// the read arrays, the staged reads each region's fetch returns (assembly_region_iterator.rs:54-159 without BAM I/O);
+    /// `capacity` / `required`: regions, membership entries; f32 arrays as `c_void`, the threshold an f64 that holds an f32
+    pub fn phmm_assembly_regions(
+        h: *mut phmm_handle,
+        n_profiles: u32,
+        n_windows: u32,
+        n_samples: u32,
+        assembly_region_extension: u32,
+        min_region_size: u32,
+        max_region_size: u32,
+        max_prob_propagation: u32,
+        active_prob_threshold: f64,
+        max_input_depth: u32,
+        n_prob: u32,
+        profile_prob: *const c_void,
+        profile_first: *const u32,
+        profile_len: *const u32,
+        profile_start: *const u64,
+        profile_stop: *const u64,
+        profile_contig_length: *const u64,
+        profile_window: *const u32,
+        group_read_off: *const u32,
+        read_pos: *const i64,
+        read_cigar_off: *const u32,
+        read_cigar: *const u32,
+        read_off: *const u32,
+        read_quals: *const u8,
+        capacity: *const u32,
+        required: *mut u32,
+        profile_status: *mut i32,
+        profile_region_off: *mut u32,
+        region_start: *mut u64,
+        region_end: *mut u64,
+        region_padded_start: *mut u64,
+        region_padded_end: *mut u64,
+        region_states: *mut u32,
+        region_flags: *mut u32,
+        region_density: *mut c_void,
+        region_n_reads: *mut u32,
+        region_read_off: *mut u32,
+        region_reads: *mut u32,
+        read_mean_qual: *mut f64,
+    ) -> c_int;
 
     pub fn phmm_set_switch(h: *mut phmm_handle, name: *const c_char, value: c_int) -> c_int;
     pub fn phmm_get_stat(h: *mut phmm_handle, name: *const c_char) -> u64;
     /// (developer runs: the task records of the device's region server, 72 bytes each)
     pub fn phmm_server_trace(device_id: c_int, out: *mut c_void, cap: u32) -> u32;
-    /// "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> server=<hash> sw=<hash> trim=<hash>": the kernel sources the library was built from
+    /// "activity=<hash> asm=<hash> cigar=<hash> events=<hash> finalize=<hash> genotype=<hash> pairhmm=<hash> phase=<hash> regions=<hash> server=<hash> sw=<hash> trim=<hash>": the kernel sources the library was built from
     pub fn phmm_build_info() -> *const c_char;
 
     pub fn phmm_table_eps(eps: *mut *const f64) -> usize;

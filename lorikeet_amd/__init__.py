@@ -10,6 +10,7 @@ from .finalize import finalize_reads  # noqa: F401
 from .phase import phase_calls  # noqa: F401
 from .assembly import assembly_kmers  # noqa: F401
 from .trim import trim_regions  # noqa: F401
+from .assembly_regions import assembly_regions  # noqa: F401
 from .batch import Read, RegionBatch  # noqa: F401
 from .engine import HipPairHMMEngine, PhmmError  # noqa: F401
 from .events import discover_events  # noqa: F401
