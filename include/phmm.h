@@ -1169,8 +1169,8 @@ int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32_t *region_
  * phmm_assembly_kmers -- what the reference's read-threading assembler decides from k-mers alone, in front of the graph, for
  * many regions and several k in ONE call: the sequences add_read makes of each read, the non-unique k-mers, where each sequence
  * starts threading and which positions it visits, how many k-mers kmer_to_vertex_map will hold, and the verdicts that reject a
- * k before a vertex exists.  The graph itself -- vertices, edges, multiplicities, pruning, dangling ends, paths -- stays the
- * caller's.  Integers and bytes: every output EQUALS the reference's.  R = src/read_threading/read_threading_graph.rs,
+ * k before a vertex exists.  The raw graph -- vertices, edges, multiplicities -- is phmm_assembly_graph's, which runs this stage
+ * inside; pruning, dangling ends and paths stay the caller's.  Integers and bytes: every output EQUALS the reference's.  R = src/read_threading/read_threading_graph.rs,
  * A = src/read_threading/read_threading_assembler.rs, K = src/assembly/kmer.rs.  Per region and k, as written:
  *   sequences    create_graph (A:924-1089) adds the reference as one sequence (start 0, stop len), then add_read per read
  *                (R:341-390): each maximal run of bases with to_ascii_uppercase(base) != 'N' and qual >= min_base_quality
@@ -1248,6 +1248,78 @@ int phmm_assembly_kmers(phmm_handle *h, uint32_t n_regions, const uint32_t *regi
                         const uint32_t *k, uint32_t min_base_quality, uint32_t *flags, uint32_t *n_sequences,
                         uint32_t *n_non_unique, uint32_t *n_tracked, uint32_t *n_distinct, uint8_t *ref_kmer_flags,
                         uint8_t *read_kmer_flags, uint32_t *ref_kmer_id, uint32_t *read_kmer_id);
+
+/*
+ * phmm_assembly_graph -- the raw read-threading graph per (k, region), exactly as it stands right after
+ * build_graph_if_necessary (R:417-477, called at A:1020): before prune_low_weight_chains, the cycle checks and dangling-end
+ * recovery, for many regions and several k in ONE call.  It runs phmm_assembly_kmers' stage inside and builds on its state.
+ * Integers and bytes: every output EQUALS the reference's, petgraph's NodeIndex and EdgeIndex included.  R, A, K as above,
+ * E = src/graphs/multi_sample_edge.rs.  Default modes only: start_threading_only_at_existing_vertex = false,
+ * increase_counts_through_branches = false, INCREASE_COUNTS_BACKWARDS = true, count = 1 per sequence.  LEFT OUT, the
+ * caller's: the other settings of those modes, and everything behind the raw graph (pruning, cycles, dangling ends, paths).
+ * Kmer equality is of bytes, not of SipHash values, as in phmm_assembly_kmers.  As written:
+ *   order        the reference is threaded first, then the sample groups in order of the first read THAT YIELDS A SEQUENCE AT
+ *                THAT K (pending.entry, R:328, a LinkedHashMap), reads in input order inside a group, a read's runs in order.
+ *                The group order can differ between two k of one region
+ *   vertices     thread_sequence (R:484-561): the start's vertex is the map's or a new one (R:597-605); extend_chain_by_one
+ *                (R:700-769) follows the out-edge whose target has the next base as its suffix, else merges into the map's
+ *                vertex for the k-mer -- never for the reference-source k-mer (R:613-618) -- else creates one; a non-unique
+ *                k-mer is never in the map (R:635-639), so it gets a vertex per (vertex before it, last base)
+ *   edges        one per (source, target); is_ref is the creating sequence's; multiplicity counts the traversals (the inherent
+ *                MultiSampleEdge::inc_multiplicity, E:89-92) plus the backward walk's
+ *   backward     increase_counts_in_matched_kmers (R:641-687) from the start vertex with offset k - 2 (none for k = 1): while
+ *                the vertex has exactly ONE in-edge at that moment and the edge's source has the suffix sequence[offset], the
+ *                edge gains 1 and the walk goes on from the source with offset - 1.  sequence is the WHOLE sequence (R:504), so
+ *                the offset counts from its first base whatever the start position.  Kept as written
+ *   pruning      E:57-96: the heap starts with the creation's count, every group's end from the creator's group on pushes the
+ *                edge's count inside that group (R:454-456 flushes every edge that exists, the reference's group too), the
+ *                lowest leaves once capacity + 1 are held; edge_pruning_multiplicity is the lowest left
+ * Inputs as phmm_assembly_kmers takes them, and
+ *   read_sample [n_reads] or NULL (one sample)   any values; reads with equal values inside a region are one sample
+ *   num_pruning_samples   1 .. PHMM_GRAPH_MAX_PRUNING_SAMPLES (the reference's default is 1)
+ * Outputs.  A graph is a (k, region) pair in k-major order, o = k index * n_regions + region, n_graphs = n_k * n_regions:
+ *   flags [n_graphs]   PHMM_ASM_REF_SHORT / _REF_NON_UNIQUE / _LOW_COMPLEXITY as phmm_assembly_kmers reports them.  A REF_SHORT
+ *                graph is empty; the other two are still built
+ *   n_vertices, n_edges, n_ref_path [n_graphs];  vertex_off, edge_off, ref_path_off [n_graphs+1]
+ *   per vertex, in NodeIndex order, at vertex_off[o] + index:  vertex_seq  0 = the reference, 1 + r = read r of the region;
+ *                vertex_pos  the creating occurrence, counted in the sequence (the read's window): the vertex's bytes are that
+ *                sequence's [pos, pos + k), its suffix the last of them;  vertex_flags  PHMM_GRAPH_VERTEX_TRACKED = it is in
+ *                kmer_to_vertex_map (what R:473-476 marks with "+"), PHMM_GRAPH_VERTEX_REF_SOURCE = the reference's first vertex
+ *   per edge, in EdgeIndex order, at edge_off[o] + index:  edge_src, edge_dst (vertex indices inside the graph), edge_is_ref
+ *                (bytes), edge_multiplicity, edge_pruning_multiplicity
+ *   ref_path     reference_path as written (R:525-548): the vertex of every reference position 0 ..= len - k; empty for a
+ *                reference of exactly k bases, where R:492 returns first, and for REF_SHORT
+ *   ref_vertex [n_k x region_ref_off[n_regions]], read_vertex [n_k x read_off[n_reads]]   both NULL (not written) or k-major
+ *                planes over ref_bases / read_bases as given: the vertex index a visited position lands on, UINT32_MAX
+ *                elsewhere.  A later stage walks reads through the graph with these and needs no bytes
+ * capacity [3] / required [3] count vertices, edges and ref_path entries, as phmm_assembly_regions does: when a capacity is too
+ * small the call returns PHMM_ERR_EVENT_CAPACITY with `required` filled and nothing else written; all capacities 0 is the
+ * way to ask, and the per-vertex, per-edge and ref_path arrays may then be NULL.
+ * Limits: phmm_assembly_kmers' for bases and positions; PHMM_GRAPH_MAX_SAMPLES distinct read_sample values per region.  Device
+ * workspace kept by the handle on top of phmm_assembly_kmers': 193 bytes per base and k (handles and edge slots per
+ * position, the trie and edge tables, stamps and in-edges per vertex slot) and 28 per read and k; behind the sizes, 4 bytes
+ * per edge and (1 + the region's samples), and the outputs.
+ * The result is the same from run to run and whatever else is in the batch: which position claims a slot of a table is a
+ * race that no output shows; the other atomics are minima and integer sums.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): every case of phmm_assembly_kmers (with
+ * ref_vertex / read_vertex for its id planes); num_pruning_samples outside its range; more than PHMM_GRAPH_MAX_SAMPLES samples
+ * in a region; one vertex plane without the other; capacity or required NULL; a capacity above 0 whose arrays are NULL.
+ * n_regions == 0 (required = {0, 0, 0}, the offset arrays hold their 0), regions without reads and empty reads are fine.  One
+ * thread per handle.  Switch "asm_fingerprint_bits" (tests) cuts the trie table's fingerprints too.
+ */
+#define PHMM_GRAPH_MAX_SAMPLES 64u
+#define PHMM_GRAPH_MAX_PRUNING_SAMPLES 8u
+#define PHMM_GRAPH_VERTEX_TRACKED 1u
+#define PHMM_GRAPH_VERTEX_REF_SOURCE 2u
+int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
+                        const uint32_t *region_read_off, const uint32_t *read_off, const uint8_t *read_bases,
+                        const uint8_t *read_quals, const uint32_t *read_first, const uint32_t *read_len,
+                        const uint32_t *read_sample, uint32_t n_k, const uint32_t *k, uint32_t min_base_quality,
+                        uint32_t num_pruning_samples, const uint32_t *capacity, uint32_t *required, uint32_t *flags,
+                        uint32_t *n_vertices, uint32_t *n_edges, uint32_t *n_ref_path, uint32_t *vertex_off, uint32_t *edge_off,
+                        uint32_t *ref_path_off, uint32_t *vertex_seq, uint32_t *vertex_pos, uint8_t *vertex_flags,
+                        uint32_t *edge_src, uint32_t *edge_dst, uint8_t *edge_is_ref, uint32_t *edge_multiplicity,
+                        uint32_t *edge_pruning_multiplicity, uint32_t *ref_path, uint32_t *ref_vertex, uint32_t *read_vertex);
 
 /*
  * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
@@ -1448,7 +1520,7 @@ int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32_t n_window
  *                  "region_sw_all" (pairs up to which a lone launched call aligns every read against every haplotype beside the
  *                  PairHMM kernels: -1 by load, 0 never), "region_flag_wait", "region_pick_timeout_us", "region_debug_pick" (tests),
  *                  "mirror_canary", "region_own_queue" (environment only)
- *   assembly       "asm_fingerprint_bits" (tests: the bits phmm_assembly_kmers keeps of a fingerprint, 0 = all 64)
+ *   assembly       "asm_fingerprint_bits" (tests: the bits phmm_assembly_kmers and phmm_assembly_graph keep of a fingerprint, 0 = all 64)
  *   many callers   "route_shared" (opt-in: private handles' small calls through the shared combiner)
  * Value -1 / 0 = back to the planner's choice as documented there.  Not to be called while another thread computes on the handle.
  * Returns PHMM_ERR_INVALID_ARG for an unknown name.

@@ -1316,6 +1316,191 @@ pub fn assembly_kmers(
         .collect()
 }
 
+/// One vertex of a raw read-threading graph: the occurrence that created it (`seq` 0 = the reference, 1 + r = read r of the
+/// region; `pos` inside that sequence, so its bytes are `[pos, pos + k)`), whether `kmer_to_vertex_map` holds it and whether it
+/// is the reference source.
+pub struct AssemblyGraphVertex {
+    pub seq: usize,
+    pub pos: usize,
+    pub tracked: bool,
+    pub ref_source: bool,
+}
+
+/// One edge of a raw read-threading graph, as `MultiSampleEdge` holds it after `build_graph_if_necessary`.
+pub struct AssemblyGraphEdge {
+    pub source: usize,
+    pub target: usize,
+    pub is_ref: bool,
+    pub multiplicity: usize,
+    pub pruning_multiplicity: usize,
+}
+
+/// What `assembly_graph` returns for one k of one region: vertices in `NodeIndex` order, edges in `EdgeIndex` order,
+/// `reference_path`, and per position of the reference and of every read (over its bases as given) the vertex it lands on,
+/// `u32::MAX` where `thread_sequence` does not visit it.
+pub struct AssemblyGraph {
+    pub k: usize,
+    pub ref_short: bool,
+    pub ref_non_unique: bool,
+    pub low_complexity: bool,
+    pub vertices: Vec<AssemblyGraphVertex>,
+    pub edges: Vec<AssemblyGraphEdge>,
+    pub reference_path: Vec<u32>,
+    pub ref_vertex: Vec<u32>,
+    pub read_vertex: Vec<Vec<u32>>,
+}
+
+/// The raw graph `ReadThreadingAssembler::create_graph` holds right after `build_graph_if_necessary`, for a batch of regions and
+/// every k in `ks` (ascending), with the default modes (dangling-branch recovery on, no counts through branches).  `samples`: a
+/// sample index per read in input order, `None`: one sample; `windows` as `assembly_kmers` takes them.  Pruning, the cycle
+/// checks, dangling ends and paths stay with the caller.  Returns `[region][k]`.
+pub fn assembly_graph(
+    regions: &[AssemblyKmerRegion],
+    ks: &[usize],
+    min_base_quality: u8,
+    windows: Option<&[(u32, u32)]>,
+    samples: Option<&[u32]>,
+    num_pruning_samples: usize,
+) -> Vec<Vec<AssemblyGraph>> {
+    let n_regions = regions.len();
+    let (mut region_ref_off, mut region_read_off, mut read_off) = (vec![0u32], vec![0u32], vec![0u32]);
+    let (mut ref_bases, mut read_bases, mut read_quals) = (Vec::<u8>::new(), Vec::<u8>::new(), Vec::<u8>::new());
+    for g in regions {
+        ref_bases.extend_from_slice(g.reference);
+        region_ref_off.push(ref_bases.len() as u32);
+        for (bases, quals) in g.reads.iter() {
+            assert_eq!(bases.len(), quals.len());
+            read_bases.extend_from_slice(bases);
+            read_quals.extend_from_slice(quals);
+            read_off.push(read_bases.len() as u32);
+        }
+        region_read_off.push((read_off.len() - 1) as u32);
+    }
+    let k32: Vec<u32> = ks.iter().map(|&k| k as u32).collect();
+    let n_k = k32.len();
+    let n_graphs = n_k * n_regions;
+    let (n_ref, n_read) = (ref_bases.len(), read_bases.len());
+    let read_first: Vec<u32> = windows.unwrap_or(&[]).iter().map(|w| w.0).collect();
+    let read_len: Vec<u32> = windows.unwrap_or(&[]).iter().map(|w| w.1).collect();
+    if let Some(w) = windows {
+        assert_eq!(w.len(), read_off.len() - 1);
+    }
+    if let Some(s) = samples {
+        assert_eq!(s.len(), read_off.len() - 1);
+    }
+    let or_null = |v: &Vec<u32>| if windows.is_some() { v.as_ptr() } else { std::ptr::null() };
+    let (mut flags, mut n_vertices, mut n_edges, mut n_ref_path) =
+        (vec![0u32; n_graphs], vec![0u32; n_graphs], vec![0u32; n_graphs], vec![0u32; n_graphs]);
+    let (mut vertex_off, mut edge_off, mut ref_path_off) = (vec![0u32; n_graphs + 1], vec![0u32; n_graphs + 1], vec![0u32; n_graphs + 1]);
+    let (mut ref_vertex, mut read_vertex) = (vec![u32::MAX; n_k * n_ref], vec![u32::MAX; n_k * n_read]);
+    let (mut vertex_seq, mut vertex_pos, mut vertex_flags) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u8>::new());
+    let (mut edge_src, mut edge_dst, mut edge_is_ref) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u8>::new());
+    let (mut edge_multiplicity, mut edge_pruning, mut ref_path) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u32>::new());
+    let mut capacity = [0u32; 3];
+    let mut required = [0u32; 3];
+    with_engine(|h| {
+        for pass in 0..2 {
+            let rc = unsafe {
+                phmm_assembly_graph(
+                    h,
+                    n_regions as u32,
+                    region_ref_off.as_ptr(),
+                    ref_bases.as_ptr(),
+                    region_read_off.as_ptr(),
+                    read_off.as_ptr(),
+                    read_bases.as_ptr(),
+                    read_quals.as_ptr(),
+                    or_null(&read_first),
+                    or_null(&read_len),
+                    if let Some(s) = samples { s.as_ptr() } else { std::ptr::null() },
+                    n_k as u32,
+                    k32.as_ptr(),
+                    min_base_quality as u32,
+                    num_pruning_samples as u32,
+                    capacity.as_ptr(),
+                    required.as_mut_ptr(),
+                    flags.as_mut_ptr(),
+                    n_vertices.as_mut_ptr(),
+                    n_edges.as_mut_ptr(),
+                    n_ref_path.as_mut_ptr(),
+                    vertex_off.as_mut_ptr(),
+                    edge_off.as_mut_ptr(),
+                    ref_path_off.as_mut_ptr(),
+                    vertex_seq.as_mut_ptr(),
+                    vertex_pos.as_mut_ptr(),
+                    vertex_flags.as_mut_ptr(),
+                    edge_src.as_mut_ptr(),
+                    edge_dst.as_mut_ptr(),
+                    edge_is_ref.as_mut_ptr(),
+                    edge_multiplicity.as_mut_ptr(),
+                    edge_pruning.as_mut_ptr(),
+                    ref_path.as_mut_ptr(),
+                    ref_vertex.as_mut_ptr(),
+                    read_vertex.as_mut_ptr(),
+                )
+            };
+            if rc == PHMM_ERR_EVENT_CAPACITY && pass == 0 {
+                capacity = required;
+                let (nv, ne, np) = (required[0] as usize, required[1] as usize, required[2] as usize);
+                vertex_seq = vec![0u32; nv];
+                vertex_pos = vec![0u32; nv];
+                vertex_flags = vec![0u8; nv];
+                edge_src = vec![0u32; ne];
+                edge_dst = vec![0u32; ne];
+                edge_is_ref = vec![0u8; ne];
+                edge_multiplicity = vec![0u32; ne];
+                edge_pruning = vec![0u32; ne];
+                ref_path = vec![0u32; np];
+                continue;
+            }
+            if rc != PHMM_OK {
+                panic!("HIP assembly_graph failed ({}): {}", rc, last_error(h));
+            }
+            break;
+        }
+    });
+    (0..n_regions)
+        .map(|g| {
+            (0..n_k)
+                .map(|i| {
+                    let o = i * n_regions + g;
+                    let (r0, r1) = (region_ref_off[g] as usize, region_ref_off[g + 1] as usize);
+                    let reads = region_read_off[g] as usize..region_read_off[g + 1] as usize;
+                    let span = |r: usize| i * n_read + read_off[r] as usize..i * n_read + read_off[r + 1] as usize;
+                    let vertices = vertex_off[o] as usize..vertex_off[o + 1] as usize;
+                    let edges = edge_off[o] as usize..edge_off[o + 1] as usize;
+                    AssemblyGraph {
+                        k: ks[i],
+                        ref_short: flags[o] & PHMM_ASM_REF_SHORT != 0,
+                        ref_non_unique: flags[o] & PHMM_ASM_REF_NON_UNIQUE != 0,
+                        low_complexity: flags[o] & PHMM_ASM_LOW_COMPLEXITY != 0,
+                        vertices: vertices
+                            .map(|v| AssemblyGraphVertex {
+                                seq: vertex_seq[v] as usize,
+                                pos: vertex_pos[v] as usize,
+                                tracked: vertex_flags[v] as u32 & PHMM_GRAPH_VERTEX_TRACKED != 0,
+                                ref_source: vertex_flags[v] as u32 & PHMM_GRAPH_VERTEX_REF_SOURCE != 0,
+                            })
+                            .collect(),
+                        edges: edges
+                            .map(|e| AssemblyGraphEdge {
+                                source: edge_src[e] as usize,
+                                target: edge_dst[e] as usize,
+                                is_ref: edge_is_ref[e] != 0,
+                                multiplicity: edge_multiplicity[e] as usize,
+                                pruning_multiplicity: edge_pruning[e] as usize,
+                            })
+                            .collect(),
+                        reference_path: ref_path[ref_path_off[o] as usize..ref_path_off[o + 1] as usize].to_vec(),
+                        ref_vertex: ref_vertex[i * n_ref + r0..i * n_ref + r1].to_vec(),
+                        read_vertex: reads.map(|r| read_vertex[span(r)].to_vec()).collect(),
+                    }
+                })
+                .collect()
+        })
+        .collect()
+}
+
 /// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
 /// location (closed) and whether it is the reference haplotype.
 pub struct TrimHaplotype<'a> {

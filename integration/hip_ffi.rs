@@ -143,6 +143,11 @@ pub const PHMM_ASM_KMER_NON_UNIQUE: c_uint = 1;
 pub const PHMM_ASM_KMER_THREADED: c_uint = 2;
 pub const PHMM_ASM_KMER_THREAD_START: c_uint = 4;
 pub const PHMM_ASM_KMER_FIRST: c_uint = 8;
+/// `phmm_assembly_graph`: its limits and the flags per vertex
+pub const PHMM_GRAPH_MAX_SAMPLES: c_uint = 64;
+pub const PHMM_GRAPH_MAX_PRUNING_SAMPLES: c_uint = 8;
+pub const PHMM_GRAPH_VERTEX_TRACKED: c_uint = 1;
+pub const PHMM_GRAPH_VERTEX_REF_SOURCE: c_uint = 2;
 /// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
 /// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
 pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
@@ -973,6 +978,47 @@ extern "C" {
         read_kmer_flags: *mut u8,
         ref_kmer_id: *mut u32,
         read_kmer_id: *mut u32,
+    ) -> c_int;
+    /// the raw read-threading graph per (k, region) as build_graph_if_necessary leaves it (read_threading_graph.rs:417-477, :484-769;
+    /// multi_sample_edge.rs), default modes: vertices in NodeIndex order, edges in EdgeIndex order with both multiplicities, the
+    /// reference path, and on request the vertex of every visited position; `capacity` / `required`: vertices, edges, ref_path
+    /// entries; `read_sample`, `read_first` / `read_len` and the two vertex planes may be null
+    pub fn phmm_assembly_graph(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_read_off: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_quals: *const u8,
+        read_first: *const u32,
+        read_len: *const u32,
+        read_sample: *const u32,
+        n_k: u32,
+        k: *const u32,
+        min_base_quality: u32,
+        num_pruning_samples: u32,
+        capacity: *const u32,
+        required: *mut u32,
+        flags: *mut u32,
+        n_vertices: *mut u32,
+        n_edges: *mut u32,
+        n_ref_path: *mut u32,
+        vertex_off: *mut u32,
+        edge_off: *mut u32,
+        ref_path_off: *mut u32,
+        vertex_seq: *mut u32,
+        vertex_pos: *mut u32,
+        vertex_flags: *mut u8,
+        edge_src: *mut u32,
+        edge_dst: *mut u32,
+        edge_is_ref: *mut u8,
+        edge_multiplicity: *mut u32,
+        edge_pruning_multiplicity: *mut u32,
+        ref_path: *mut u32,
+        ref_vertex: *mut u32,
+        read_vertex: *mut u32,
     ) -> c_int;
     /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
     /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;

@@ -48,6 +48,7 @@ PHMM_PH_NO_TRIM, PHMM_PH_ABORTED, PHMM_PH_GT_01, PHMM_PH_GT_10 = 1, 1, 0, 1
 PHMM_ASM_MAX_K_VALUES, PHMM_ASM_MAX_K, PHMM_ASM_MAX_REF_BASES, PHMM_ASM_MAX_READ_BASES, PHMM_ASM_MAX_POSITIONS = 8, 255, 16384, 16384, 536870912
 PHMM_ASM_REF_SHORT, PHMM_ASM_REF_NON_UNIQUE, PHMM_ASM_LOW_COMPLEXITY = 1, 2, 4
 PHMM_ASM_KMER_NON_UNIQUE, PHMM_ASM_KMER_THREADED, PHMM_ASM_KMER_THREAD_START, PHMM_ASM_KMER_FIRST = 1, 2, 4, 8
+PHMM_GRAPH_MAX_SAMPLES, PHMM_GRAPH_MAX_PRUNING_SAMPLES, PHMM_GRAPH_VERTEX_TRACKED, PHMM_GRAPH_VERTEX_REF_SOURCE = 64, 8, 1, 2
 PHMM_REG_ACTIVE, PHMM_REG_FORCED, PHMM_REG_OVER_DEPTH = 1, 2, 4
 PHMM_REG_STATUS_MIN_REGION_SIZE, PHMM_REG_STATUS_START_PAST_CONTIG = -1, -2
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
@@ -182,6 +183,9 @@ SYMBOLS = [
                                    C.POINTER(C.c_int64), u32p, u32p, u8p, C.POINTER(C.c_int32)]),
     ("phmm_assembly_kmers", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
                                       u32p, u32p, u32p, u32p, u32p, u8p, u8p, u32p, u32p]),
+    ("phmm_assembly_graph", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
+                                      C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u8p, u32p, u32p, u8p,
+                                      u32p, u32p, u32p, u32p, u32p]),
     ("phmm_trim_regions", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
                                     u64p, u64p, u8p, C.c_uint32, u32p, C.POINTER(C.c_int32), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
                                     u64p, u64p, C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u32p, u32p, u32p, u32p, u8p,

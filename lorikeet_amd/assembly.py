@@ -1,6 +1,7 @@
 """The k-mer stage in front of the read-threading graph on the device (phmm_assembly_kmers, include/phmm.h): per region and k
 the verdicts that reject a k before a vertex exists, the sizes of the non-unique set and of the vertex map, and per position
-whether its k-mer is non-unique, threaded, a threading start, the first of its bytes, with its dense id."""
+whether its k-mer is non-unique, threaded, a threading start, the first of its bytes, with its dense id; and the raw
+read-threading graph itself (phmm_assembly_graph): vertices, edges, weights, the reference path, per (k, region)."""
 import ctypes as C
 
 import numpy as np
@@ -82,5 +83,78 @@ def assembly_kmers(engine, regions, k, min_base_quality=10, read_first=None, rea
     for name, n in (("ref_kmer_flags", n_ref), ("read_kmer_flags", n_read), ("ref_kmer_id", n_ref), ("read_kmer_id", n_read)):
         if o[name] is not None:
             o[name] = o[name].reshape(n_k, n)
+    o.update(region_ref_off=region_ref_off, region_read_off=region_read_off, read_off=read_off, k=k)
+    return o
+
+
+GRAPH_SIZES = ("flags", "n_vertices", "n_edges", "n_ref_path")
+GRAPH_OFFSETS = ("vertex_off", "edge_off", "ref_path_off")
+GRAPH_VERTEX = (("vertex_seq", np.uint32), ("vertex_pos", np.uint32), ("vertex_flags", np.uint8))
+GRAPH_EDGE = (("edge_src", np.uint32), ("edge_dst", np.uint32), ("edge_is_ref", np.uint8), ("edge_multiplicity", np.uint32),
+              ("edge_pruning_multiplicity", np.uint32))
+GRAPH_OUTPUTS = GRAPH_SIZES + GRAPH_OFFSETS + tuple(n for n, _ in GRAPH_VERTEX + GRAPH_EDGE) + ("ref_path", "ref_vertex", "read_vertex")
+
+
+def assembly_graph(engine, regions, k, min_base_quality=10, read_first=None, read_len=None, read_sample=None, num_pruning_samples=1,
+                   planes=True, capacity=None, fill=None, omit=()):
+    """The raw read-threading graph of every (k, region) of a batch (phmm_assembly_graph).  regions, k, read_first / read_len as
+    assembly_kmers takes them; read_sample: a value per read, None = one sample; planes=False: the vertex planes are not asked
+    for (None in the result); capacity: (vertices, edges, ref_path entries), None asks the library first (a call with capacities
+    0); fill: a byte the output arrays hold before the call, omit: names of arrays to pass as NULL (tests).  Returns a dict of
+    numpy arrays: flags, n_vertices, n_edges, n_ref_path [n_k, n_regions]; vertex_off, edge_off, ref_path_off [n_k * n_regions +
+    1]; the per-vertex, per-edge and ref_path arrays cut to what was written; ref_vertex [n_k, reference bases], read_vertex
+    [n_k, read bases]; required.  Raises PhmmError; after PHMM_ERR_EVENT_CAPACITY its `required` attribute holds the sizes."""
+    a = regions if isinstance(regions, dict) else pack(regions)
+    u32 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint32)  # noqa: E731
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8)  # noqa: E731
+    region_ref_off, region_read_off, read_off = u32(a.get("region_ref_off")), u32(a.get("region_read_off")), u32(a.get("read_off"))
+    ref_bases, read_bases, read_quals = u8(a.get("ref_bases")), u8(a.get("read_bases")), u8(a.get("read_quals"))
+    read_first, read_len, read_sample = u32(read_first), u32(read_len), u32(read_sample)
+    k = np.ascontiguousarray(k, np.uint32).reshape(-1)
+    n_k = len(k)
+    n_regions = next((len(x) - 1 for x in (region_ref_off, region_read_off) if x is not None), 0)
+    n_graphs = n_k * n_regions
+    n_ref = int(region_ref_off[-1]) if n_regions and region_ref_off is not None else 0
+    n_read = int(read_off[-1]) if read_off is not None and len(read_off) else 0
+    new = lambda n, dt: np.zeros(n, dt) if fill is None else np.frombuffer(bytes([fill]) * (n * np.dtype(dt).itemsize), dt).copy()  # noqa: E731
+
+    def call(cap):
+        cap = np.ascontiguousarray(cap, np.uint32)
+        o = dict(required=new(3, np.uint32))
+        o.update({name: new(n_graphs, np.uint32) for name in GRAPH_SIZES})
+        o.update({name: new(n_graphs + 1, np.uint32) for name in GRAPH_OFFSETS})
+        o.update({name: new(int(cap[0]), dt) if cap[0] else None for name, dt in GRAPH_VERTEX})
+        o.update({name: new(int(cap[1]), dt) if cap[1] else None for name, dt in GRAPH_EDGE})
+        o.update(ref_path=new(int(cap[2]), np.uint32) if cap[2] else None,
+                 ref_vertex=new(n_k * n_ref, np.uint32) if planes else None, read_vertex=new(n_k * n_read, np.uint32) if planes else None)
+        for name in omit:
+            o[name] = None
+        ptr = lambda name: _p(o[name], _lib.u8p if o[name] is not None and o[name].dtype == np.uint8 else _lib.u32p)  # noqa: E731
+        code = engine.lib.phmm_assembly_graph(
+            engine._h, n_regions, _p(region_ref_off, _lib.u32p), _p(ref_bases, _lib.u8p), _p(region_read_off, _lib.u32p),
+            _p(read_off, _lib.u32p), _p(read_bases, _lib.u8p), _p(read_quals, _lib.u8p), _p(read_first, _lib.u32p), _p(read_len, _lib.u32p),
+            _p(read_sample, _lib.u32p), n_k, _p(k, _lib.u32p), int(min_base_quality), int(num_pruning_samples),
+            None if "capacity" in omit else _p(cap, _lib.u32p), ptr("required"), *[ptr(name) for name in GRAPH_OUTPUTS])
+        return code, o
+
+    if capacity is None:
+        code, o = call((0, 0, 0))
+        if code == _lib.PHMM_ERR_EVENT_CAPACITY:
+            code, o = call(o["required"])
+    else:
+        code, o = call(capacity)
+    if code != _lib.PHMM_OK:
+        err = PhmmError(code, engine.last_error())
+        err.required = None if o["required"] is None else o["required"].copy()
+        err.outputs = {name: v for name, v in o.items() if v is not None and name != "required"}
+        raise err
+    V, E, P = (int(x) for x in o["required"])
+    for name in GRAPH_SIZES:
+        o[name] = o[name].reshape(n_k, n_regions)
+    for names, n in ((GRAPH_VERTEX, V), (GRAPH_EDGE, E), ((("ref_path", np.uint32),), P)):
+        for name, dt in names:
+            o[name] = np.zeros(0, dt) if o[name] is None else o[name][:n]
+    if planes:
+        o["ref_vertex"], o["read_vertex"] = o["ref_vertex"].reshape(n_k, n_ref), o["read_vertex"].reshape(n_k, n_read)
     o.update(region_ref_off=region_ref_off, region_read_off=region_read_off, read_off=read_off, k=k)
     return o

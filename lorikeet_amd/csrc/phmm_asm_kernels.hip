@@ -20,49 +20,7 @@ namespace phmm {
 
 namespace {
 
-struct Seq {
-    const uint8_t *bases;
-    uint64_t *hash;   // len + 1 entries
-    uint32_t len;
-    uint32_t plane;   // where it starts in its plane (ref_bases or read_bases)
-    uint32_t region;
-};
-
-__device__ inline Seq ref_seq(const AsmParams &p, uint32_t g) {
-    const uint32_t o = p.region_ref_off[g];
-    return {p.ref_bases + o, p.ref_hash + o + g, p.region_ref_off[g + 1] - o, o, g};
-}
-
-__device__ inline Seq read_seq(const AsmParams &p, uint32_t r) {
-    const uint32_t o = p.read_begin[r];
-    return {p.read_bases + o, p.read_hash + o + r, p.read_len[r], o, p.read_region[r]};
-}
-
-__device__ inline uint32_t ref_len(const AsmParams &p, uint32_t g) { return p.region_ref_off[g + 1] - p.region_ref_off[g]; }
-
-__device__ inline uint64_t mix64(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
-// the fingerprint of the k bytes at pos: two loads and a multiply, for any k, from the one prefix hash
-__device__ inline uint64_t fingerprint(const AsmParams &p, const uint64_t *hash, uint32_t pos, uint32_t kk) {
-    return mix64(hash[pos + p.k[kk]] - hash[pos] * p.base_pow[kk]) & p.fp_mask;
-}
-
-__device__ inline uint32_t home_slot(uint64_t fp, uint32_t cap) {
-    return __umulhi((uint32_t)(fp >> 32) + (uint32_t)fp * 0x9e3779b1u, cap);
-}
-
-__device__ inline bool same_bytes(const uint8_t *a, const uint8_t *b, uint32_t k) {
-    for (uint32_t i = 0; i < k; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
-}
+using namespace asm_device;
 
 __device__ inline bool usable(const AsmParams &p, const uint8_t *bases, const uint8_t *quals, uint32_t i) {
     return (bases[i] & 0xdf) != 'N' && quals[i] >= p.min_base_quality;   // read_threading_graph.rs:400-403

@@ -159,6 +159,7 @@ struct phmm_handle {
     } gwork;
     // grow-only staging of phmm_allele_frequency (phmm_af.cpp), phmm_annotate_events (phmm_annotate.cpp), phmm_assign_genotypes (phmm_assign.cpp)
     StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging, asm_staging, trim_staging;
+    StagingBuffer graph_staging;  // phmm_assembly_graph (phmm_graph.cpp): its second half, sized once the graphs' sizes are known
     // phmm_assembly_regions (phmm_regions.cpp): per state and read, per region, per membership -- each sized once its count is known
     StagingBuffer regions_staging, regions_out_staging, regions_reads_staging;
     // phmm_discover_events' device-only workspace (phmm_events.cpp), which phmm_trim_regions (phmm_trim.cpp) shares: grow-only, no host mirror
