@@ -1322,6 +1322,67 @@ int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uint32_t *regi
                         uint32_t *edge_pruning_multiplicity, uint32_t *ref_path, uint32_t *ref_vertex, uint32_t *read_vertex);
 
 /*
+ * phmm_assembly_prune -- what create_graph does to the raw graph before it looks for paths (A:1041-1073, A:1118-1136), for many
+ * graphs in ONE call: prune_low_weight_chains with the production pruner (the low-weight one; the adaptive pruner is LEFT OUT),
+ * the orphans, the cycle verdict, the reference ends, the vertices dangling-end recovery starts from, and
+ * remove_paths_not_connected_to_ref.  Integers and bytes: every output EQUALS the reference's.  A, R as above,
+ * C = src/graphs/chain_pruner.rs, L = src/graphs/low_weight_chain_pruner.rs, B = src/graphs/base_graph.rs.  Degrees count
+ * edges.  Three graphs: G0 = the input without its absent elements; G1 = G0 after CHAINS if asked, else G0; G2 = G1 after
+ * CONNECT if asked, else G1.
+ *   CHAINS       (C:39-56) a vertex is interior if its in-degree and its out-degree are 1.  An edge's chain head is the edge
+ *                itself if its source is not interior, else the head of the source's one in-edge; an edge on a ring of interior
+ *                vertices has none.  find_all_chains (C:58-80) finds a head exactly when its source can be reached in G0 from
+ *                a vertex of in-degree 0; a component without such a vertex yields no chain and loses nothing.  A found chain
+ *                is removed if every edge of it has pruning multiplicity < prune_factor and is not is_ref (L:24-36): nothing
+ *                with factor 0.  Then every vertex without an edge is removed unless G0 has exactly one vertex (B:392-406:
+ *                the orphans are listed before any is removed, and is_ref_source of an isolated vertex asks for a node count
+ *                of 1)
+ *   on G1        PHMM_PRUNE_HAS_CYCLE: a directed cycle, a self-loop included (B:615-617).  ref_source / ref_sink: the lowest
+ *                vertex index for which is_ref_source / is_ref_sink holds (B:339-387, B:411-428), its "the graph has one node"
+ *                evaluated on G1; UINT32_MAX if there is none, and PHMM_PRUNE_NO_REF_ENDS if either is missing.  Per vertex
+ *                PHMM_PRUNE_DANGLING_TAIL: out-degree 0 and not is_ref_sink (R:792-797); PHMM_PRUNE_DANGLING_HEAD: in-degree 0
+ *                and not is_ref_source (R:837-842)
+ *   CONNECT      (B:626-656) every vertex of G1 goes, with its edges, unless it can be reached forwards from ref_source AND
+ *                backwards from ref_sink.  A graph with NO_REF_ENDS stays G1 (the reference panics there)
+ * The LOW_COMPLEXITY verdict of A:1066 is the flag phmm_assembly_graph already reports: pruning changes neither
+ * non_unique_kmers nor kmer_to_vertex_map, so it is not computed again here.
+ * Inputs: the arrays as phmm_assembly_graph writes them,
+ *   vertex_off, edge_off [n_graphs+1]; edge_src, edge_dst (indices inside the graph), edge_is_ref, edge_pruning_multiplicity
+ *   vertex_absent, edge_absent   both NULL or both given: a nonzero byte marks an element that is not in the graph (a vacant
+ *                slot of a StableGraph), so that a second call can run on a graph the caller has changed -- CONNECT comes
+ *                behind dangling-end recovery
+ *   ops          PHMM_PRUNE_OP_CHAINS | PHMM_PRUNE_OP_CONNECT
+ *   prune_factor [n_graphs]   the coverage correction of A:245-255 is the caller's arithmetic
+ * Outputs:
+ *   graph_flags, n_chains (found), n_chains_removed, n_vertices_left, n_edges_left (of G2), ref_source, ref_sink [n_graphs]
+ *   edge_chain [edges]   the head's EdgeIndex; UINT32_MAX for an edge in no found chain, and everywhere without CHAINS
+ *   edge_state [edges], vertex_state [vertices]   PHMM_PRUNE_ABSENT (as given), _REMOVED_CHAINS, _REMOVED_CONNECT; on vertices
+ *                the two dangling bits too (of G1, whatever CONNECT removes)
+ * Device workspace kept by the handle: 20 bytes per vertex and 5 per edge, beside the staged arrays.  One workgroup works on a
+ * graph, so a call with one huge graph runs on one compute unit.  The result is the same from run to run: the atomics are
+ * integer sums, ORs and minima, and a mark is only ever set.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): ops 0 or with unknown bits; one mask without
+ * the other; a NULL array that has elements; offsets that do not start at 0 or decrease; an endpoint >= the graph's
+ * n_vertices; a present edge with an absent endpoint.  n_graphs == 0, graphs without vertices and graphs without edges are
+ * fine.  One thread per handle.
+ */
+#define PHMM_PRUNE_OP_CHAINS 1u
+#define PHMM_PRUNE_OP_CONNECT 2u
+#define PHMM_PRUNE_HAS_CYCLE 1u
+#define PHMM_PRUNE_NO_REF_ENDS 2u
+#define PHMM_PRUNE_ABSENT 1u
+#define PHMM_PRUNE_REMOVED_CHAINS 2u
+#define PHMM_PRUNE_REMOVED_CONNECT 4u
+#define PHMM_PRUNE_DANGLING_TAIL 8u
+#define PHMM_PRUNE_DANGLING_HEAD 16u
+int phmm_assembly_prune(phmm_handle *h, uint32_t n_graphs, const uint32_t *vertex_off, const uint32_t *edge_off,
+                        const uint32_t *edge_src, const uint32_t *edge_dst, const uint8_t *edge_is_ref,
+                        const uint32_t *edge_pruning_multiplicity, const uint8_t *vertex_absent, const uint8_t *edge_absent,
+                        uint32_t ops, const uint32_t *prune_factor, uint32_t *graph_flags, uint32_t *n_chains,
+                        uint32_t *n_chains_removed, uint32_t *n_vertices_left, uint32_t *n_edges_left, uint32_t *ref_source,
+                        uint32_t *ref_sink, uint32_t *edge_chain, uint8_t *edge_state, uint8_t *vertex_state);
+
+/*
  * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
  * assembler's haplotypes before a likelihood is computed, for many regions in ONE call: get_variation_events, the trimmer's
  * two spans, every haplotype cut to the padded span, duplicates folded, the rest in the reference's order.  Integers and

@@ -1501,6 +1501,113 @@ pub fn assembly_graph(
         .collect()
 }
 
+/// What `assembly_prune` returns for one graph.  `edge_chain[e]` is the `EdgeIndex` of the head of the chain `find_all_chains`
+/// puts edge `e` in, `u32::MAX` for an edge in no chain; `edge_state` and `vertex_state` hold `PHMM_PRUNE_*` bits.
+pub struct PrunedGraph {
+    pub has_cycle: bool,
+    pub no_ref_ends: bool,
+    pub n_chains: usize,
+    pub n_chains_removed: usize,
+    pub n_vertices_left: usize,
+    pub n_edges_left: usize,
+    pub ref_source: Option<usize>,
+    pub ref_sink: Option<usize>,
+    pub edge_chain: Vec<u32>,
+    pub edge_state: Vec<u8>,
+    pub vertex_state: Vec<u8>,
+}
+
+/// What `create_graph` does to the raw graphs of `assembly_graph` before it looks for paths: `prune_low_weight_chains` with the
+/// low-weight pruner and one factor per graph (`PHMM_PRUNE_OP_CHAINS`), `has_cycles`, the reference ends, the vertices
+/// dangling-end recovery starts from, and `remove_paths_not_connected_to_ref` (`PHMM_PRUNE_OP_CONNECT`).  `absent`: per graph
+/// the vertices and the edges that are vacant slots by now, `None`: none are.  The adaptive pruner, dangling-end recovery
+/// itself and paths stay with the caller.
+pub fn assembly_prune(
+    graphs: &[&AssemblyGraph],
+    prune_factors: &[usize],
+    ops: u32,
+    absent: Option<&[(Vec<u8>, Vec<u8>)]>,
+) -> Vec<PrunedGraph> {
+    let n_graphs = graphs.len();
+    assert_eq!(prune_factors.len(), n_graphs);
+    let (mut vertex_off, mut edge_off) = (vec![0u32], vec![0u32]);
+    let (mut edge_src, mut edge_dst, mut edge_is_ref, mut edge_pruning) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u8>::new(), Vec::<u32>::new());
+    let (mut vertex_absent, mut edge_absent) = (Vec::<u8>::new(), Vec::<u8>::new());
+    for (i, g) in graphs.iter().enumerate() {
+        for e in g.edges.iter() {
+            edge_src.push(e.source as u32);
+            edge_dst.push(e.target as u32);
+            edge_is_ref.push(e.is_ref as u8);
+            edge_pruning.push(e.pruning_multiplicity as u32);
+        }
+        if let Some(a) = absent {
+            assert_eq!((a[i].0.len(), a[i].1.len()), (g.vertices.len(), g.edges.len()));
+            vertex_absent.extend_from_slice(&a[i].0);
+            edge_absent.extend_from_slice(&a[i].1);
+        }
+        vertex_off.push(vertex_off[i] + g.vertices.len() as u32);
+        edge_off.push(edge_src.len() as u32);
+    }
+    let factor: Vec<u32> = prune_factors.iter().map(|&f| f.min(u32::MAX as usize) as u32).collect();
+    let (n_v, n_e) = (vertex_off[n_graphs] as usize, edge_src.len());
+    let or_null = |v: &Vec<u8>| if absent.is_some() { v.as_ptr() } else { std::ptr::null() };
+    let (mut graph_flags, mut n_chains, mut n_chains_removed) = (vec![0u32; n_graphs], vec![0u32; n_graphs], vec![0u32; n_graphs]);
+    let (mut n_vertices_left, mut n_edges_left) = (vec![0u32; n_graphs], vec![0u32; n_graphs]);
+    let (mut ref_source, mut ref_sink) = (vec![u32::MAX; n_graphs], vec![u32::MAX; n_graphs]);
+    let (mut edge_chain, mut edge_state, mut vertex_state) = (vec![u32::MAX; n_e], vec![0u8; n_e], vec![0u8; n_v]);
+    with_engine(|h| {
+        let rc = unsafe {
+            phmm_assembly_prune(
+                h,
+                n_graphs as u32,
+                vertex_off.as_ptr(),
+                edge_off.as_ptr(),
+                edge_src.as_ptr(),
+                edge_dst.as_ptr(),
+                edge_is_ref.as_ptr(),
+                edge_pruning.as_ptr(),
+                or_null(&vertex_absent),
+                or_null(&edge_absent),
+                ops,
+                factor.as_ptr(),
+                graph_flags.as_mut_ptr(),
+                n_chains.as_mut_ptr(),
+                n_chains_removed.as_mut_ptr(),
+                n_vertices_left.as_mut_ptr(),
+                n_edges_left.as_mut_ptr(),
+                ref_source.as_mut_ptr(),
+                ref_sink.as_mut_ptr(),
+                edge_chain.as_mut_ptr(),
+                edge_state.as_mut_ptr(),
+                vertex_state.as_mut_ptr(),
+            )
+        };
+        if rc != PHMM_OK {
+            panic!("HIP assembly_prune failed ({}): {}", rc, last_error(h));
+        }
+    });
+    let index = |v: u32| if v == u32::MAX { None } else { Some(v as usize) };
+    (0..n_graphs)
+        .map(|o| {
+            let vertices = vertex_off[o] as usize..vertex_off[o + 1] as usize;
+            let edges = edge_off[o] as usize..edge_off[o + 1] as usize;
+            PrunedGraph {
+                has_cycle: graph_flags[o] & PHMM_PRUNE_HAS_CYCLE != 0,
+                no_ref_ends: graph_flags[o] & PHMM_PRUNE_NO_REF_ENDS != 0,
+                n_chains: n_chains[o] as usize,
+                n_chains_removed: n_chains_removed[o] as usize,
+                n_vertices_left: n_vertices_left[o] as usize,
+                n_edges_left: n_edges_left[o] as usize,
+                ref_source: index(ref_source[o]),
+                ref_sink: index(ref_sink[o]),
+                edge_chain: edge_chain[edges.clone()].to_vec(),
+                edge_state: edge_state[edges].to_vec(),
+                vertex_state: vertex_state[vertices].to_vec(),
+            }
+        })
+        .collect()
+}
+
 /// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
 /// location (closed) and whether it is the reference haplotype.
 pub struct TrimHaplotype<'a> {

@@ -148,6 +148,16 @@ pub const PHMM_GRAPH_MAX_SAMPLES: c_uint = 64;
 pub const PHMM_GRAPH_MAX_PRUNING_SAMPLES: c_uint = 8;
 pub const PHMM_GRAPH_VERTEX_TRACKED: c_uint = 1;
 pub const PHMM_GRAPH_VERTEX_REF_SOURCE: c_uint = 2;
+/// `phmm_assembly_prune`: the steps, the verdicts per graph, the bits per edge and per vertex
+pub const PHMM_PRUNE_OP_CHAINS: c_uint = 1;
+pub const PHMM_PRUNE_OP_CONNECT: c_uint = 2;
+pub const PHMM_PRUNE_HAS_CYCLE: c_uint = 1;
+pub const PHMM_PRUNE_NO_REF_ENDS: c_uint = 2;
+pub const PHMM_PRUNE_ABSENT: c_uint = 1;
+pub const PHMM_PRUNE_REMOVED_CHAINS: c_uint = 2;
+pub const PHMM_PRUNE_REMOVED_CONNECT: c_uint = 4;
+pub const PHMM_PRUNE_DANGLING_TAIL: c_uint = 8;
+pub const PHMM_PRUNE_DANGLING_HEAD: c_uint = 16;
 /// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
 /// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
 pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
@@ -1019,6 +1029,34 @@ extern "C" {
         ref_path: *mut u32,
         ref_vertex: *mut u32,
         read_vertex: *mut u32,
+    ) -> c_int;
+    /// what create_graph does to the raw graph before it looks for paths (read_threading_assembler.rs:1041-1073, :1118-1136), for
+    /// many graphs: low-weight chains (chain_pruner.rs:39-118, low_weight_chain_pruner.rs:24-36), orphans, the cycle verdict, the
+    /// reference ends, the dangling ends and remove_paths_not_connected_to_ref (base_graph.rs:339-428, :615-656); the two
+    /// `absent` masks are null together
+    pub fn phmm_assembly_prune(
+        h: *mut phmm_handle,
+        n_graphs: u32,
+        vertex_off: *const u32,
+        edge_off: *const u32,
+        edge_src: *const u32,
+        edge_dst: *const u32,
+        edge_is_ref: *const u8,
+        edge_pruning_multiplicity: *const u32,
+        vertex_absent: *const u8,
+        edge_absent: *const u8,
+        ops: u32,
+        prune_factor: *const u32,
+        graph_flags: *mut u32,
+        n_chains: *mut u32,
+        n_chains_removed: *mut u32,
+        n_vertices_left: *mut u32,
+        n_edges_left: *mut u32,
+        ref_source: *mut u32,
+        ref_sink: *mut u32,
+        edge_chain: *mut u32,
+        edge_state: *mut u8,
+        vertex_state: *mut u8,
     ) -> c_int;
     /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
     /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;

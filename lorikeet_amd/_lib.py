@@ -49,6 +49,8 @@ PHMM_ASM_MAX_K_VALUES, PHMM_ASM_MAX_K, PHMM_ASM_MAX_REF_BASES, PHMM_ASM_MAX_READ
 PHMM_ASM_REF_SHORT, PHMM_ASM_REF_NON_UNIQUE, PHMM_ASM_LOW_COMPLEXITY = 1, 2, 4
 PHMM_ASM_KMER_NON_UNIQUE, PHMM_ASM_KMER_THREADED, PHMM_ASM_KMER_THREAD_START, PHMM_ASM_KMER_FIRST = 1, 2, 4, 8
 PHMM_GRAPH_MAX_SAMPLES, PHMM_GRAPH_MAX_PRUNING_SAMPLES, PHMM_GRAPH_VERTEX_TRACKED, PHMM_GRAPH_VERTEX_REF_SOURCE = 64, 8, 1, 2
+PHMM_PRUNE_OP_CHAINS, PHMM_PRUNE_OP_CONNECT, PHMM_PRUNE_HAS_CYCLE, PHMM_PRUNE_NO_REF_ENDS = 1, 2, 1, 2
+PHMM_PRUNE_ABSENT, PHMM_PRUNE_REMOVED_CHAINS, PHMM_PRUNE_REMOVED_CONNECT, PHMM_PRUNE_DANGLING_TAIL, PHMM_PRUNE_DANGLING_HEAD = 1, 2, 4, 8, 16
 PHMM_REG_ACTIVE, PHMM_REG_FORCED, PHMM_REG_OVER_DEPTH = 1, 2, 4
 PHMM_REG_STATUS_MIN_REGION_SIZE, PHMM_REG_STATUS_START_PAST_CONTIG = -1, -2
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
@@ -186,6 +188,8 @@ SYMBOLS = [
     ("phmm_assembly_graph", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
                                       C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u8p, u32p, u32p, u8p,
                                       u32p, u32p, u32p, u32p, u32p]),
+    ("phmm_assembly_prune", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u32p, u32p, u8p, u32p, u8p, u8p, C.c_uint32, u32p, u32p, u32p, u32p,
+                                      u32p, u32p, u32p, u32p, u32p, u8p, u8p]),
     ("phmm_trim_regions", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
                                     u64p, u64p, u8p, C.c_uint32, u32p, C.POINTER(C.c_int32), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
                                     u64p, u64p, C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u32p, u32p, u32p, u32p, u8p,

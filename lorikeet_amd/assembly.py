@@ -1,7 +1,8 @@
 """The k-mer stage in front of the read-threading graph on the device (phmm_assembly_kmers, include/phmm.h): per region and k
 the verdicts that reject a k before a vertex exists, the sizes of the non-unique set and of the vertex map, and per position
 whether its k-mer is non-unique, threaded, a threading start, the first of its bytes, with its dense id; and the raw
-read-threading graph itself (phmm_assembly_graph): vertices, edges, weights, the reference path, per (k, region)."""
+read-threading graph itself (phmm_assembly_graph): vertices, edges, weights, the reference path, per (k, region); and what the
+assembler prunes from it before it looks for paths (phmm_assembly_prune)."""
 import ctypes as C
 
 import numpy as np
@@ -157,4 +158,43 @@ def assembly_graph(engine, regions, k, min_base_quality=10, read_first=None, rea
     if planes:
         o["ref_vertex"], o["read_vertex"] = o["ref_vertex"].reshape(n_k, n_ref), o["read_vertex"].reshape(n_k, n_read)
     o.update(region_ref_off=region_ref_off, region_read_off=region_read_off, read_off=read_off, k=k)
+    return o
+
+
+PRUNE_GRAPH = ("graph_flags", "n_chains", "n_chains_removed", "n_vertices_left", "n_edges_left", "ref_source", "ref_sink")
+PRUNE_OUTPUTS = PRUNE_GRAPH + ("edge_chain", "edge_state", "vertex_state")
+PRUNE_ALL = _lib.PHMM_PRUNE_OP_CHAINS | _lib.PHMM_PRUNE_OP_CONNECT
+
+
+def prune_graph(engine, graph, prune_factor, ops=PRUNE_ALL, vertex_absent=None, edge_absent=None, fill=None):
+    """Low-weight chains, orphans, the cycle verdict, the reference ends, the dangling ends and the vertices off every way from
+    the reference source to the reference sink, for many graphs (phmm_assembly_prune).  graph: the dict assembly_graph returns,
+    or any dict with vertex_off, edge_off, edge_src, edge_dst, edge_is_ref, edge_pruning_multiplicity; prune_factor: one value
+    or one per graph; ops: PHMM_PRUNE_OP_* bits; vertex_absent / edge_absent: bytes, nonzero = not in the graph, both or
+    neither; fill: a byte the output arrays hold before the call (tests).  Returns a dict of numpy arrays: graph_flags,
+    n_chains, n_chains_removed, n_vertices_left, n_edges_left, ref_source, ref_sink [n_graphs]; edge_chain, edge_state [edges];
+    vertex_state [vertices].  Raises PhmmError."""
+    u32 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint32).reshape(-1)  # noqa: E731
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8).reshape(-1)  # noqa: E731
+    vertex_off, edge_off = u32(graph.get("vertex_off")), u32(graph.get("edge_off"))
+    edge_src, edge_dst, edge_mult = u32(graph.get("edge_src")), u32(graph.get("edge_dst")), u32(graph.get("edge_pruning_multiplicity"))
+    edge_is_ref, vertex_absent, edge_absent = u8(graph.get("edge_is_ref")), u8(vertex_absent), u8(edge_absent)
+    n_graphs = next((len(x) - 1 for x in (vertex_off, edge_off) if x is not None and len(x)), 0)
+    if prune_factor is not None:
+        prune_factor = np.full(n_graphs, prune_factor, np.uint32) if np.ndim(prune_factor) == 0 else u32(prune_factor)
+    # (the sizes of the outputs; with an offset array missing or broken -- the library refuses those -- any size will do)
+    n_v = int(vertex_off[-1]) if n_graphs and vertex_off is not None else 0
+    n_e = int(edge_off[-1]) if n_graphs and edge_off is not None else 0
+    new = lambda n, dt: np.zeros(n, dt) if fill is None else np.frombuffer(bytes([fill]) * (n * np.dtype(dt).itemsize), dt).copy()  # noqa: E731
+    o = {name: new(n_graphs, np.uint32) for name in PRUNE_GRAPH}
+    o.update(edge_chain=new(n_e, np.uint32), edge_state=new(n_e, np.uint8), vertex_state=new(n_v, np.uint8))
+    code = engine.lib.phmm_assembly_prune(
+        engine._h, n_graphs, _p(vertex_off, _lib.u32p), _p(edge_off, _lib.u32p), _p(edge_src, _lib.u32p), _p(edge_dst, _lib.u32p),
+        _p(edge_is_ref, _lib.u8p), _p(edge_mult, _lib.u32p), _p(vertex_absent, _lib.u8p), _p(edge_absent, _lib.u8p), int(ops),
+        _p(prune_factor, _lib.u32p), *[_p(o[name], _lib.u32p) for name in PRUNE_GRAPH], _p(o["edge_chain"], _lib.u32p),
+        _p(o["edge_state"], _lib.u8p), _p(o["vertex_state"], _lib.u8p))
+    if code != _lib.PHMM_OK:
+        err = PhmmError(code, engine.last_error())
+        err.outputs = o
+        raise err
     return o
