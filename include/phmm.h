@@ -1383,6 +1383,121 @@ int phmm_assembly_prune(phmm_handle *h, uint32_t n_graphs, const uint32_t *verte
                         uint32_t *ref_sink, uint32_t *edge_chain, uint8_t *edge_state, uint8_t *vertex_state);
 
 /*
+ * phmm_assembly_recover -- dangling-end recovery, what get_assembly_result does next (A:1118-1131): recover_dangling_tails, then
+ * recover_dangling_heads on the graph the tails left, for many graphs in ONE call.  Integers and bytes: every output EQUALS the
+ * reference's.  R = src/read_threading/read_threading_graph.rs:779-1766, B = src/graphs/base_graph.rs,
+ * T = src/read_threading/abstract_read_threading_graph.rs:91-125, 202-212, E = src/graphs/multi_sample_edge.rs.
+ * Modes: recover_all_dangling_branches = false (the default: give_up_at_branch = true in both find_path_* functions).
+ * recover_all = true is LEFT OUT; the config has no field for it.  Both head merges are in: min_matching_bases < 0 (the command
+ * line's default is -1) takes merge_dangling_head_legacy with best_prefix_match_legacy and get_max_mismatches_legacy, >= 0 takes
+ * merge_dangling_head with best_prefix_match; the tail's matching_suffix test (R:987-993) reads the same value.  As written:
+ *   order        all tails are listed in NodeIndex order before any is touched (R:792-797) and taken in that order, then the
+ *                heads likewise on the graph the tails left.  A merge changes degrees that a later end reads, so the ends of a
+ *                graph are taken strictly one after the other
+ *   find_path    R:1651-1692 in full: the low-weight reset against prune_factor, the loop check, done / return_path of
+ *                R:1505-1524 and R:1595-1614; then the is_ref_source / is_ref_sink / length refusals (R:1386-1390 with
+ *                max(1, min_dangling_branch_length) for a tail, R:1453-1457 with the length as given for a head)
+ *   reference path   downwards get_next_reference_vertex(v, true, the in-edge of alt_path[1]), upwards
+ *                get_prev_reference_vertex; edges_directed lists the NEWEST edge first, which decides among several reference
+ *                out-edges or reference-node predecessors.  An edge this call adds is newer than every edge of the input
+ *   strings      the suffix byte per vertex; for a head a vertex of in-degree 0 gives its whole k-mer reversed (R:1741-1750)
+ *   alignment    reference-path string against alt-path string, phmm_sw_align's aligner restated for LeadingInDel, then
+ *                remove_trailing_deletions; cigar_is_okay_to_merge with MAX_CIGAR_COMPLEXITY = 3
+ *   merges       merge_dangling_tail (longest_suffix_match capped by the last element, the leading-deletion correction,
+ *                ref_index_to_merge <= 0 refused), the two head merges, extend_dangling_path_against_reference (R:1209-1291: the
+ *                dangling source's out-edge goes, num_nodes_to_extend vertices with the bytes sequence_to_extend[i..i+k] are
+ *                chained by edges of the removed edge's multiplicity).  A new edge is MultiSampleEdge::new(false, multiplicity,
+ *                num_pruning_samples): its heap holds the one count, so its pruning multiplicity IS its multiplicity (E:119-131)
+ * The reuse of vacant petgraph slots by the caller's own add_edge is NOT modelled: new elements are reported in creation order,
+ * which is what a caller with a StableGraph needs (the newest edge comes first in edges_directed).
+ * cfg points to a phmm_recover_config (declared `const void *` like phmm_finalize_reads' cfg):
+ *   ops          PHMM_RECOVER_OP_TAILS | PHMM_RECOVER_OP_HEADS
+ *   min_dangling_branch_length, min_matching_bases, max_mismatches_in_dangling_head (the defaults: 4, -1, -1)
+ *   num_pruning_samples   1 .. PHMM_GRAPH_MAX_PRUNING_SAMPLES (the capacity of a new edge's heap: no output depends on it)
+ *   sw_parameters         the dangling-end Smith-Waterman parameters (STANDARD_NGS = 25, -50, -110, -6)
+ * Inputs: the region arrays as phmm_assembly_graph takes them (a vertex's bytes are vertex_seq / vertex_pos into them), n_k, k
+ * and the k-major graph layout (n_graphs = n_k * n_regions); the graph arrays as phmm_assembly_graph writes them: vertex_off,
+ * edge_off, vertex_seq, vertex_pos, edge_src, edge_dst, edge_is_ref, edge_multiplicity, edge_pruning_multiplicity;
+ *   vertex_absent, edge_absent   both NULL or both given, nonzero = not in the graph (phmm_assembly_prune's states)
+ *   graph_flags [n_graphs] or NULL   phmm_assembly_prune's: a graph with PHMM_PRUNE_HAS_CYCLE is refused (the caller drops it
+ *                before this stage).  Cycles are not looked for again: every walk ends after vertices + 1 steps
+ *   prune_factor [n_graphs]
+ * Outputs.  capacity [3] / required [3] count ends, new edges and new vertices, as phmm_assembly_graph's do: when a capacity is
+ * too small the call returns PHMM_ERR_EVENT_CAPACITY with `required` filled and nothing else written; all capacities 0 is the
+ * way to ask (the call does all its work either way: the sizes are known only once the ends have been taken).
+ *   per graph    n_tails, n_tails_recovered, n_heads, n_heads_recovered, n_new_edges, n_new_vertices, n_rounds [n_graphs];
+ *                end_off, new_edge_off, new_vertex_off [n_graphs+1].  n_rounds: the rounds a speculate-and-commit schedule
+ *                would need -- all pending ends of a kind resolved at once, committed in order up to the first end that inspected
+ *                a vertex whose edges an end of the same round changed; 1 per kind with ends where ends do not interfere
+ *   per end, in processing order   end_vertex; end_kind (PHMM_RECOVER_KIND_*); end_status (PHMM_RECOVER_END_*, one per exit of
+ *                the reference); end_alt_len, end_ref_len: the two strings' lengths (0 where none was aligned); end_n_cigar and
+ *                end_cigar [ends x 4]: the first 4 elements in BAM encoding, the trailing deletion removed; end_edge: the new
+ *                edge it made, counted inside the graph's new edges, or UINT32_MAX
+ *   per new edge, in creation order   new_edge_src, new_edge_dst (new vertices are numbered n_vertices + i inside the graph;
+ *                both UINT32_MAX for a new edge that a later extension took out again), new_edge_multiplicity,
+ *                new_edge_pruning_multiplicity; is_ref is 0 by construction
+ *   per new vertex   new_vertex_kmer [new vertices x max(k)]: its k bytes, zeros behind them.  They are no occurrence in any
+ *                input sequence
+ *   edge_removed [edges]   1 for the out-edge that an extension took out
+ * PHMM_RECOVER_END_NO_MERGE_POINT: best_prefix_match_legacy met no mismatch inside the first element, or best_prefix_match ran
+ * to an index <= 0 (R:1179-1181).  PHMM_RECOVER_END_REFERENCE_FAILS: the reference itself panics or never returns here (a merge
+ * index past the reference path at R:1031 with min_matching_bases = 0, a walk through a cycle); nothing is merged.
+ * Deviation from a batch-parallel schedule: one workgroup (one wave) works on a graph and takes its ends one after the other
+ * with an aligner of its own -- an anti-diagonal sweep, not phmm_sw_align's kernels.  A call with one huge graph runs on one
+ * compute unit.  Limits: 30 000 vertices per graph (a backtrack entry has 16 bits); max |weight| x (2 x (vertices + max k + 2)
+ * + 2) below 1e9.  Device workspace kept by the handle: 41 bytes per vertex slot and 17 per edge slot -- a graph's slots are its
+ * own plus (k + 1) edges and k vertices per candidate head and one edge per candidate tail -- and per workgroup in flight a slab
+ * of 2 (L + 1)^2 + 46 L bytes, L = the most vertices of a graph with ends + max k + 2 -- the bound of a path, not the lengths
+ * the ends turn out to have; as many workgroups run as 512 MiB of slabs allow, and at least one: a slab larger than that is
+ * allocated at its size (1.8 GB at the vertex limit), and the handle keeps half as much again.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): the cases of phmm_assembly_prune for
+ * offsets, endpoints and masks; region offsets that do not start at 0 or decrease, a read window outside its read; vertex_seq /
+ * vertex_pos outside their sequence; k outside 1 .. PHMM_ASM_MAX_K; ops 0 or with unknown bits; num_pruning_samples out of
+ * range; cfg, capacity or required NULL; a graph flagged cyclic; a graph above the limits; a capacity above 0 whose arrays are
+ * NULL.  n_graphs == 0, graphs without vertices and graphs without dangling ends are fine.  One thread per handle.
+ */
+#define PHMM_RECOVER_OP_TAILS 1u
+#define PHMM_RECOVER_OP_HEADS 2u
+#define PHMM_RECOVER_KIND_TAIL 0u
+#define PHMM_RECOVER_KIND_HEAD 1u
+#define PHMM_RECOVER_END_NO_PATH 0u
+#define PHMM_RECOVER_END_LOOP 1u
+#define PHMM_RECOVER_END_AT_REF_END 2u
+#define PHMM_RECOVER_END_TOO_SHORT 3u
+#define PHMM_RECOVER_END_CIGAR_NOT_OKAY 4u
+#define PHMM_RECOVER_END_TOO_FEW_MATCHING 5u
+#define PHMM_RECOVER_END_WHOLE_INSERTION 6u
+#define PHMM_RECOVER_END_TOO_MANY_MISMATCHES 7u
+#define PHMM_RECOVER_END_CANNOT_PUSH_REF 8u
+#define PHMM_RECOVER_END_CANNOT_EXTEND 9u
+#define PHMM_RECOVER_END_MERGED 10u
+#define PHMM_RECOVER_END_NO_MERGE_POINT 11u
+#define PHMM_RECOVER_END_REFERENCE_FAILS 12u
+typedef struct phmm_recover_config {
+    uint32_t ops;
+    int32_t min_dangling_branch_length;
+    int32_t min_matching_bases;
+    int32_t max_mismatches_in_dangling_head;
+    uint32_t num_pruning_samples;
+    phmm_sw_parameters sw_parameters;
+} phmm_recover_config;
+int phmm_assembly_recover(phmm_handle *h, const void *cfg, uint32_t n_regions, const uint32_t *region_ref_off,
+                          const uint8_t *ref_bases, const uint32_t *region_read_off, const uint32_t *read_off,
+                          const uint8_t *read_bases, const uint32_t *read_first, const uint32_t *read_len, uint32_t n_k,
+                          const uint32_t *k, const uint32_t *vertex_off, const uint32_t *edge_off, const uint32_t *vertex_seq,
+                          const uint32_t *vertex_pos, const uint32_t *edge_src, const uint32_t *edge_dst,
+                          const uint8_t *edge_is_ref, const uint32_t *edge_multiplicity,
+                          const uint32_t *edge_pruning_multiplicity, const uint8_t *vertex_absent, const uint8_t *edge_absent,
+                          const uint32_t *graph_flags, const uint32_t *prune_factor, const uint32_t *capacity, uint32_t *required,
+                          uint32_t *n_tails, uint32_t *n_tails_recovered, uint32_t *n_heads, uint32_t *n_heads_recovered,
+                          uint32_t *n_new_edges, uint32_t *n_new_vertices, uint32_t *n_rounds, uint32_t *end_off,
+                          uint32_t *new_edge_off, uint32_t *new_vertex_off, uint32_t *end_vertex, uint32_t *end_kind,
+                          uint32_t *end_status, uint32_t *end_alt_len, uint32_t *end_ref_len, uint32_t *end_n_cigar,
+                          uint32_t *end_cigar, uint32_t *end_edge, uint32_t *new_edge_src, uint32_t *new_edge_dst,
+                          uint32_t *new_edge_multiplicity, uint32_t *new_edge_pruning_multiplicity, uint8_t *new_vertex_kmer,
+                          uint8_t *edge_removed);
+
+/*
  * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
  * assembler's haplotypes before a likelihood is computed, for many regions in ONE call: get_variation_events, the trimmer's
  * two spans, every haplotype cut to the padded span, duplicates folded, the rest in the reference's order.  Integers and

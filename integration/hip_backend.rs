@@ -1608,6 +1608,163 @@ pub fn assembly_prune(
         .collect()
 }
 
+/// What `assembly_recover` returns: the arrays of `phmm_assembly_recover` as the header lays them out, cut to what was written.
+pub struct RecoveredEnds {
+    pub per_graph: Vec<[u32; 7]>,
+    pub end_off: Vec<u32>,
+    pub new_edge_off: Vec<u32>,
+    pub new_vertex_off: Vec<u32>,
+    pub end_vertex: Vec<u32>,
+    pub end_kind: Vec<u32>,
+    pub end_status: Vec<u32>,
+    pub end_alt_len: Vec<u32>,
+    pub end_ref_len: Vec<u32>,
+    pub end_n_cigar: Vec<u32>,
+    pub end_cigar: Vec<u32>,
+    pub end_edge: Vec<u32>,
+    pub new_edge_src: Vec<u32>,
+    pub new_edge_dst: Vec<u32>,
+    pub new_edge_multiplicity: Vec<u32>,
+    pub new_edge_pruning_multiplicity: Vec<u32>,
+    pub new_vertex_kmer: Vec<u8>,
+    pub edge_removed: Vec<u8>,
+}
+
+/// The dense arrays `assembly_recover` reads: the regions as `assembly_graph` packed them and the graphs as it returned them,
+/// k-major, with the masks `assembly_prune` left (empty slices: no element is absent).
+pub struct RecoverInput<'a> {
+    pub region_ref_off: &'a [u32],
+    pub ref_bases: &'a [u8],
+    pub region_read_off: &'a [u32],
+    pub read_off: &'a [u32],
+    pub read_bases: &'a [u8],
+    pub k: &'a [u32],
+    pub vertex_off: &'a [u32],
+    pub edge_off: &'a [u32],
+    pub vertex_seq: &'a [u32],
+    pub vertex_pos: &'a [u32],
+    pub edge_src: &'a [u32],
+    pub edge_dst: &'a [u32],
+    pub edge_is_ref: &'a [u8],
+    pub edge_multiplicity: &'a [u32],
+    pub edge_pruning_multiplicity: &'a [u32],
+    pub vertex_absent: &'a [u8],
+    pub edge_absent: &'a [u8],
+    pub prune_factor: &'a [u32],
+}
+
+/// Dangling-end recovery for many graphs: `recover_dangling_tails`, then `recover_dangling_heads`, with
+/// `recover_all_dangling_branches = false`.  Asks for the sizes first (capacities 0), then calls again with them.  Not compiled
+/// here and bound to no call site: the assembler's `get_assembly_result` still recovers on the host.
+pub fn assembly_recover(input: &RecoverInput, cfg: &phmm_recover_config) -> RecoveredEnds {
+    let n_regions = input.region_ref_off.len().max(1) - 1;
+    let n_graphs = input.k.len() * n_regions;
+    let k_max = input.k.iter().copied().max().unwrap_or(0) as usize;
+    let masks = !input.vertex_absent.is_empty() || !input.edge_absent.is_empty();
+    let or_null = |v: &[u8]| if masks { v.as_ptr() } else { std::ptr::null() };
+    let mut capacity = [0u32; 3];
+    let mut required = [0u32; 3];
+    loop {
+        let mut per = vec![vec![0u32; n_graphs]; 7];
+        let (mut end_off, mut new_edge_off, mut new_vertex_off) = (vec![0u32; n_graphs + 1], vec![0u32; n_graphs + 1], vec![0u32; n_graphs + 1]);
+        let mut ends = vec![vec![0u32; capacity[0] as usize]; 7];
+        let mut end_cigar = vec![0u32; 4 * capacity[0] as usize];
+        let mut edges = vec![vec![0u32; capacity[1] as usize]; 4];
+        let mut new_vertex_kmer = vec![0u8; capacity[2] as usize * k_max];
+        let mut edge_removed = vec![0u8; input.edge_src.len()];
+        let mut rc = PHMM_OK;
+        with_engine(|h| {
+            rc = unsafe {
+                phmm_assembly_recover(
+                    h,
+                    cfg as *const phmm_recover_config as *const std::os::raw::c_void,
+                    n_regions as u32,
+                    input.region_ref_off.as_ptr(),
+                    input.ref_bases.as_ptr(),
+                    input.region_read_off.as_ptr(),
+                    input.read_off.as_ptr(),
+                    input.read_bases.as_ptr(),
+                    std::ptr::null(),
+                    std::ptr::null(),
+                    input.k.len() as u32,
+                    input.k.as_ptr(),
+                    input.vertex_off.as_ptr(),
+                    input.edge_off.as_ptr(),
+                    input.vertex_seq.as_ptr(),
+                    input.vertex_pos.as_ptr(),
+                    input.edge_src.as_ptr(),
+                    input.edge_dst.as_ptr(),
+                    input.edge_is_ref.as_ptr(),
+                    input.edge_multiplicity.as_ptr(),
+                    input.edge_pruning_multiplicity.as_ptr(),
+                    or_null(input.vertex_absent),
+                    or_null(input.edge_absent),
+                    std::ptr::null(),
+                    input.prune_factor.as_ptr(),
+                    capacity.as_ptr(),
+                    required.as_mut_ptr(),
+                    per[0].as_mut_ptr(),
+                    per[1].as_mut_ptr(),
+                    per[2].as_mut_ptr(),
+                    per[3].as_mut_ptr(),
+                    per[4].as_mut_ptr(),
+                    per[5].as_mut_ptr(),
+                    per[6].as_mut_ptr(),
+                    end_off.as_mut_ptr(),
+                    new_edge_off.as_mut_ptr(),
+                    new_vertex_off.as_mut_ptr(),
+                    ends[0].as_mut_ptr(),
+                    ends[1].as_mut_ptr(),
+                    ends[2].as_mut_ptr(),
+                    ends[3].as_mut_ptr(),
+                    ends[4].as_mut_ptr(),
+                    ends[5].as_mut_ptr(),
+                    end_cigar.as_mut_ptr(),
+                    ends[6].as_mut_ptr(),
+                    edges[0].as_mut_ptr(),
+                    edges[1].as_mut_ptr(),
+                    edges[2].as_mut_ptr(),
+                    edges[3].as_mut_ptr(),
+                    new_vertex_kmer.as_mut_ptr(),
+                    edge_removed.as_mut_ptr(),
+                )
+            };
+            if rc != PHMM_OK && rc != PHMM_ERR_EVENT_CAPACITY {
+                panic!("HIP assembly_recover failed ({}): {}", rc, last_error(h));
+            }
+        });
+        if rc == PHMM_ERR_EVENT_CAPACITY {
+            capacity = required;
+            continue;
+        }
+        let mut edges = edges.into_iter();
+        let mut ends = ends.into_iter();
+        let mut next_end = || ends.next().unwrap();
+        let (end_vertex, end_kind, end_status, end_alt_len, end_ref_len, end_n_cigar, end_edge) =
+            (next_end(), next_end(), next_end(), next_end(), next_end(), next_end(), next_end());
+        return RecoveredEnds {
+            per_graph: (0..n_graphs).map(|g| [per[0][g], per[1][g], per[2][g], per[3][g], per[4][g], per[5][g], per[6][g]]).collect(),
+            end_off,
+            new_edge_off,
+            new_vertex_off,
+            end_vertex,
+            end_kind,
+            end_status,
+            end_alt_len,
+            end_ref_len,
+            end_n_cigar,
+            end_cigar,
+            end_edge,
+            new_edge_src: edges.next().unwrap(),
+            new_edge_dst: edges.next().unwrap(),
+            new_edge_multiplicity: edges.next().unwrap(),
+            new_edge_pruning_multiplicity: edges.next().unwrap(),
+            new_vertex_kmer,
+            edge_removed,
+        };
+    }
+}
+
 /// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
 /// location (closed) and whether it is the reference haplotype.
 pub struct TrimHaplotype<'a> {

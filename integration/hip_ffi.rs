@@ -158,6 +158,24 @@ pub const PHMM_PRUNE_REMOVED_CHAINS: c_uint = 2;
 pub const PHMM_PRUNE_REMOVED_CONNECT: c_uint = 4;
 pub const PHMM_PRUNE_DANGLING_TAIL: c_uint = 8;
 pub const PHMM_PRUNE_DANGLING_HEAD: c_uint = 16;
+/// `phmm_assembly_recover`: the steps, an end's kind, and one status per exit of the reference's recovery
+pub const PHMM_RECOVER_OP_TAILS: c_uint = 1;
+pub const PHMM_RECOVER_OP_HEADS: c_uint = 2;
+pub const PHMM_RECOVER_KIND_TAIL: c_uint = 0;
+pub const PHMM_RECOVER_KIND_HEAD: c_uint = 1;
+pub const PHMM_RECOVER_END_NO_PATH: c_uint = 0;
+pub const PHMM_RECOVER_END_LOOP: c_uint = 1;
+pub const PHMM_RECOVER_END_AT_REF_END: c_uint = 2;
+pub const PHMM_RECOVER_END_TOO_SHORT: c_uint = 3;
+pub const PHMM_RECOVER_END_CIGAR_NOT_OKAY: c_uint = 4;
+pub const PHMM_RECOVER_END_TOO_FEW_MATCHING: c_uint = 5;
+pub const PHMM_RECOVER_END_WHOLE_INSERTION: c_uint = 6;
+pub const PHMM_RECOVER_END_TOO_MANY_MISMATCHES: c_uint = 7;
+pub const PHMM_RECOVER_END_CANNOT_PUSH_REF: c_uint = 8;
+pub const PHMM_RECOVER_END_CANNOT_EXTEND: c_uint = 9;
+pub const PHMM_RECOVER_END_MERGED: c_uint = 10;
+pub const PHMM_RECOVER_END_NO_MERGE_POINT: c_uint = 11;
+pub const PHMM_RECOVER_END_REFERENCE_FAILS: c_uint = 12;
 /// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
 /// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
 pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
@@ -190,6 +208,18 @@ pub struct phmm_finalize_config {
     pub dont_use_soft_clipped_bases: u8,
     pub half_of_pcr_snv_qual: u8,
     pub reserved: u8,
+}
+
+/// `phmm_recover_config`: which ends `phmm_assembly_recover` takes, and the reference's parameters of dangling-end recovery
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct phmm_recover_config {
+    pub ops: u32,
+    pub min_dangling_branch_length: i32,
+    pub min_matching_bases: i32,
+    pub max_mismatches_in_dangling_head: i32,
+    pub num_pruning_samples: u32,
+    pub sw_parameters: phmm_sw_parameters,
 }
 
 /// `phmm_realign_config`: what `realign_reads_to_their_best_haplotype` fixes at its call site
@@ -1057,6 +1087,62 @@ extern "C" {
         edge_chain: *mut u32,
         edge_state: *mut u8,
         vertex_state: *mut u8,
+    ) -> c_int;
+    /// dangling-end recovery (read_threading_graph.rs:779-1766): recover_dangling_tails, then recover_dangling_heads, for many
+    /// graphs, every end of a graph after the one before it; `cfg` points to a `phmm_recover_config`; the two `absent` masks are
+    /// null together, `graph_flags` may be null; `capacity` / `required` count ends, new edges and new vertices
+    pub fn phmm_assembly_recover(
+        h: *mut phmm_handle,
+        cfg: *const c_void,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_read_off: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_first: *const u32,
+        read_len: *const u32,
+        n_k: u32,
+        k: *const u32,
+        vertex_off: *const u32,
+        edge_off: *const u32,
+        vertex_seq: *const u32,
+        vertex_pos: *const u32,
+        edge_src: *const u32,
+        edge_dst: *const u32,
+        edge_is_ref: *const u8,
+        edge_multiplicity: *const u32,
+        edge_pruning_multiplicity: *const u32,
+        vertex_absent: *const u8,
+        edge_absent: *const u8,
+        graph_flags: *const u32,
+        prune_factor: *const u32,
+        capacity: *const u32,
+        required: *mut u32,
+        n_tails: *mut u32,
+        n_tails_recovered: *mut u32,
+        n_heads: *mut u32,
+        n_heads_recovered: *mut u32,
+        n_new_edges: *mut u32,
+        n_new_vertices: *mut u32,
+        n_rounds: *mut u32,
+        end_off: *mut u32,
+        new_edge_off: *mut u32,
+        new_vertex_off: *mut u32,
+        end_vertex: *mut u32,
+        end_kind: *mut u32,
+        end_status: *mut u32,
+        end_alt_len: *mut u32,
+        end_ref_len: *mut u32,
+        end_n_cigar: *mut u32,
+        end_cigar: *mut u32,
+        end_edge: *mut u32,
+        new_edge_src: *mut u32,
+        new_edge_dst: *mut u32,
+        new_edge_multiplicity: *mut u32,
+        new_edge_pruning_multiplicity: *mut u32,
+        new_vertex_kmer: *mut u8,
+        edge_removed: *mut u8,
     ) -> c_int;
     /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
     /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;

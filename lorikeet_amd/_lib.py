@@ -51,6 +51,10 @@ PHMM_ASM_KMER_NON_UNIQUE, PHMM_ASM_KMER_THREADED, PHMM_ASM_KMER_THREAD_START, PH
 PHMM_GRAPH_MAX_SAMPLES, PHMM_GRAPH_MAX_PRUNING_SAMPLES, PHMM_GRAPH_VERTEX_TRACKED, PHMM_GRAPH_VERTEX_REF_SOURCE = 64, 8, 1, 2
 PHMM_PRUNE_OP_CHAINS, PHMM_PRUNE_OP_CONNECT, PHMM_PRUNE_HAS_CYCLE, PHMM_PRUNE_NO_REF_ENDS = 1, 2, 1, 2
 PHMM_PRUNE_ABSENT, PHMM_PRUNE_REMOVED_CHAINS, PHMM_PRUNE_REMOVED_CONNECT, PHMM_PRUNE_DANGLING_TAIL, PHMM_PRUNE_DANGLING_HEAD = 1, 2, 4, 8, 16
+PHMM_RECOVER_OP_TAILS, PHMM_RECOVER_OP_HEADS, PHMM_RECOVER_KIND_TAIL, PHMM_RECOVER_KIND_HEAD = 1, 2, 0, 1
+(PHMM_RECOVER_END_NO_PATH, PHMM_RECOVER_END_LOOP, PHMM_RECOVER_END_AT_REF_END, PHMM_RECOVER_END_TOO_SHORT, PHMM_RECOVER_END_CIGAR_NOT_OKAY,
+ PHMM_RECOVER_END_TOO_FEW_MATCHING, PHMM_RECOVER_END_WHOLE_INSERTION, PHMM_RECOVER_END_TOO_MANY_MISMATCHES, PHMM_RECOVER_END_CANNOT_PUSH_REF,
+ PHMM_RECOVER_END_CANNOT_EXTEND, PHMM_RECOVER_END_MERGED, PHMM_RECOVER_END_NO_MERGE_POINT, PHMM_RECOVER_END_REFERENCE_FAILS) = range(13)
 PHMM_REG_ACTIVE, PHMM_REG_FORCED, PHMM_REG_OVER_DEPTH = 1, 2, 4
 PHMM_REG_STATUS_MIN_REGION_SIZE, PHMM_REG_STATUS_START_PAST_CONTIG = -1, -2
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
@@ -75,6 +79,12 @@ class RealignConfig(C.Structure):
     """phmm_realign_config (include/phmm.h)."""
     _fields_ = [("sw_parameters", SwParameters), ("overhang_strategy", C.c_int32), ("flags", C.c_uint32),
                 ("informative_threshold", C.c_double)]
+
+
+class RecoverConfig(C.Structure):
+    """phmm_recover_config (include/phmm.h)."""
+    _fields_ = [("ops", C.c_uint32), ("min_dangling_branch_length", C.c_int32), ("min_matching_bases", C.c_int32),
+                ("max_mismatches_in_dangling_head", C.c_int32), ("num_pruning_samples", C.c_uint32), ("sw_parameters", SwParameters)]
 
 
 class FinalizeConfig(C.Structure):
@@ -190,6 +200,8 @@ SYMBOLS = [
                                       u32p, u32p, u32p, u32p, u32p]),
     ("phmm_assembly_prune", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u32p, u32p, u8p, u32p, u8p, u8p, C.c_uint32, u32p, u32p, u32p, u32p,
                                       u32p, u32p, u32p, u32p, u32p, u8p, u8p]),
+    ("phmm_assembly_recover", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u32p, u32p, C.c_uint32, u32p, u32p, u32p, u32p,
+                                        u32p, u32p, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, u32p, u32p] + [u32p] * 22 + [u8p, u8p]),
     ("phmm_trim_regions", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
                                     u64p, u64p, u8p, C.c_uint32, u32p, C.POINTER(C.c_int32), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
                                     u64p, u64p, C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u32p, u32p, u32p, u32p, u8p,

@@ -198,3 +198,135 @@ def prune_graph(engine, graph, prune_factor, ops=PRUNE_ALL, vertex_absent=None, 
         err.outputs = o
         raise err
     return o
+
+
+RECOVER_GRAPH = ("n_tails", "n_tails_recovered", "n_heads", "n_heads_recovered", "n_new_edges", "n_new_vertices", "n_rounds")
+RECOVER_OFFSETS = ("end_off", "new_edge_off", "new_vertex_off")
+RECOVER_END = ("end_vertex", "end_kind", "end_status", "end_alt_len", "end_ref_len", "end_n_cigar", "end_cigar", "end_edge")
+RECOVER_EDGE = ("new_edge_src", "new_edge_dst", "new_edge_multiplicity", "new_edge_pruning_multiplicity")
+RECOVER_OUTPUTS = RECOVER_GRAPH + RECOVER_OFFSETS + RECOVER_END + RECOVER_EDGE + ("new_vertex_kmer", "edge_removed")
+RECOVER_ALL = _lib.PHMM_RECOVER_OP_TAILS | _lib.PHMM_RECOVER_OP_HEADS
+_GONE = _lib.PHMM_PRUNE_ABSENT | _lib.PHMM_PRUNE_REMOVED_CHAINS | _lib.PHMM_PRUNE_REMOVED_CONNECT
+
+
+def recover_dangling_ends(engine, regions, graph, pruned, prune_factor, ops=RECOVER_ALL, min_dangling_branch_length=4, min_matching_bases=-1,
+                          max_mismatches_in_dangling_head=-1, num_pruning_samples=1, sw_parameters=(25, -50, -110, -6), read_first=None,
+                          read_len=None, capacity=None, fill=None, omit=()):
+    """Dangling-end recovery for many graphs (phmm_assembly_recover): recover_dangling_tails, then recover_dangling_heads.
+    regions: what assembly_graph was given (a list of (reference, reads), or pack()'s dict); graph: the dict assembly_graph
+    returns (k, vertex_off, edge_off, vertex_seq, vertex_pos and the edge arrays); pruned: the dict prune_graph returns -- its
+    vertex_state / edge_state make the absent masks and its graph_flags travel along -- or None for the graph as it is, or a dict
+    with vertex_absent / edge_absent; prune_factor: one value or one per graph; read_first / read_len: the windows assembly_graph
+    was given; capacity: (ends, new edges, new vertices), None asks the library first (a call with capacities 0); fill: a byte the
+    output arrays hold before the call, omit: names of arrays to pass as NULL (tests).  Returns a dict of numpy arrays: n_tails,
+    n_tails_recovered, n_heads, n_heads_recovered, n_new_edges, n_new_vertices, n_rounds [n_graphs]; end_off, new_edge_off,
+    new_vertex_off [n_graphs + 1]; the per-end and per-new-edge arrays cut to what was written (end_cigar [ends, 4]);
+    new_vertex_kmer [new vertices, max k]; edge_removed [edges]; required.  Raises PhmmError; after PHMM_ERR_EVENT_CAPACITY its
+    `required` attribute holds the sizes."""
+    a = regions if isinstance(regions, dict) else pack(regions)
+    u32 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint32).reshape(-1)  # noqa: E731
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8).reshape(-1)  # noqa: E731
+    region_ref_off, region_read_off, read_off = u32(a.get("region_ref_off")), u32(a.get("region_read_off")), u32(a.get("read_off"))
+    ref_bases, read_bases = u8(a.get("ref_bases")), u8(a.get("read_bases"))
+    read_first, read_len = u32(read_first), u32(read_len)
+    k = u32(graph.get("k"))
+    n_k = 0 if k is None else len(k)
+    n_regions = next((len(x) - 1 for x in (region_ref_off, region_read_off) if x is not None), 0)
+    n_graphs = n_k * n_regions
+    g32 = {name: u32(graph.get(name)) for name in ("vertex_off", "edge_off", "vertex_seq", "vertex_pos", "edge_src", "edge_dst", "edge_multiplicity",
+                                                   "edge_pruning_multiplicity")}
+    edge_is_ref = u8(graph.get("edge_is_ref"))
+    vertex_absent = edge_absent = graph_flags = None
+    if pruned is not None:
+        if "vertex_state" in pruned:
+            vertex_absent, edge_absent = u8((np.asarray(pruned["vertex_state"]) & _GONE) != 0), u8((np.asarray(pruned["edge_state"]) & _GONE) != 0)
+        else:
+            vertex_absent, edge_absent = u8(pruned.get("vertex_absent")), u8(pruned.get("edge_absent"))
+        graph_flags = u32(pruned.get("graph_flags"))
+    if prune_factor is not None:
+        prune_factor = np.full(n_graphs, prune_factor, np.uint32) if np.ndim(prune_factor) == 0 else u32(prune_factor)
+    cfg = _lib.RecoverConfig(int(ops), int(min_dangling_branch_length), int(min_matching_bases), int(max_mismatches_in_dangling_head),
+                             int(num_pruning_samples), _lib.SwParameters(*[int(x) for x in sw_parameters]))
+    n_e = int(g32["edge_off"][-1]) if n_graphs and g32["edge_off"] is not None and len(g32["edge_off"]) else 0
+    k_max = int(k.max()) if n_k else 0
+    new = lambda n, dt: np.zeros(n, dt) if fill is None else np.frombuffer(bytes([fill]) * (n * np.dtype(dt).itemsize), dt).copy()  # noqa: E731
+
+    def call(cap):
+        cap = np.ascontiguousarray(cap, np.uint32)
+        o = dict(required=new(3, np.uint32))
+        o.update({name: new(n_graphs, np.uint32) for name in RECOVER_GRAPH})
+        o.update({name: new(n_graphs + 1, np.uint32) for name in RECOVER_OFFSETS})
+        o.update({name: new(int(cap[0]) * (4 if name == "end_cigar" else 1), np.uint32) if cap[0] else None for name in RECOVER_END})
+        o.update({name: new(int(cap[1]), np.uint32) if cap[1] else None for name in RECOVER_EDGE})
+        o.update(new_vertex_kmer=new(int(cap[2]) * k_max, np.uint8) if cap[2] else None, edge_removed=new(n_e, np.uint8))
+        for name in omit:
+            o[name] = None
+        ptr = lambda name: _p(o[name], _lib.u8p if o[name] is not None and o[name].dtype == np.uint8 else _lib.u32p)  # noqa: E731
+        code = engine.lib.phmm_assembly_recover(
+            engine._h, None if "cfg" in omit else C.byref(cfg), n_regions, _p(region_ref_off, _lib.u32p), _p(ref_bases, _lib.u8p),
+            _p(region_read_off, _lib.u32p), _p(read_off, _lib.u32p), _p(read_bases, _lib.u8p), _p(read_first, _lib.u32p), _p(read_len, _lib.u32p),
+            n_k, _p(k, _lib.u32p), *[_p(g32[name], _lib.u32p) for name in ("vertex_off", "edge_off", "vertex_seq", "vertex_pos", "edge_src", "edge_dst")],
+            _p(edge_is_ref, _lib.u8p), _p(g32["edge_multiplicity"], _lib.u32p), _p(g32["edge_pruning_multiplicity"], _lib.u32p),
+            _p(vertex_absent, _lib.u8p), _p(edge_absent, _lib.u8p), _p(graph_flags, _lib.u32p), _p(prune_factor, _lib.u32p),
+            None if "capacity" in omit else _p(cap, _lib.u32p), ptr("required"), *[ptr(name) for name in RECOVER_OUTPUTS])
+        return code, o
+
+    if capacity is None:
+        code, o = call((0, 0, 0))
+        if code == _lib.PHMM_ERR_EVENT_CAPACITY:
+            code, o = call(o["required"])
+    else:
+        code, o = call(capacity)
+    if code != _lib.PHMM_OK:
+        err = PhmmError(code, engine.last_error())
+        err.required = None if o["required"] is None else o["required"].copy()
+        err.outputs = {name: v for name, v in o.items() if v is not None and name != "required"}
+        raise err
+    n_end, n_edge, n_vertex = (int(x) for x in o["required"])
+    for name in RECOVER_END:
+        width = 4 if name == "end_cigar" else 1
+        o[name] = np.zeros(0, np.uint32) if o[name] is None else o[name][:n_end * width]
+    o["end_cigar"] = o["end_cigar"].reshape(-1, 4)
+    for name in RECOVER_EDGE:
+        o[name] = np.zeros(0, np.uint32) if o[name] is None else o[name][:n_edge]
+    o["new_vertex_kmer"] = (np.zeros(0, np.uint8) if o["new_vertex_kmer"] is None else o["new_vertex_kmer"][:n_vertex * k_max]).reshape(n_vertex, k_max)
+    return o
+
+
+def apply_recovery(graph, pruned, recovered):
+    """The graphs after recovery, ready for prune_graph(..., ops=PHMM_PRUNE_OP_CONNECT): a dict with vertex_off, edge_off, edge_src,
+    edge_dst, edge_is_ref, edge_multiplicity, edge_pruning_multiplicity -- every graph's own elements first, then what
+    recover_dangling_ends made for it, in creation order -- the two masks vertex_absent / edge_absent (what pruning removed, the
+    edges extensions took out, new edges taken out again), and new_vertex_kmer [new vertices, max k] with new_vertex_off.  graph,
+    pruned, recovered: what assembly_graph, prune_graph (or None) and recover_dangling_ends returned."""
+    vertex_off, edge_off = np.asarray(graph["vertex_off"], np.int64).reshape(-1), np.asarray(graph["edge_off"], np.int64).reshape(-1)
+    nv_off, ne_off = np.asarray(recovered["new_vertex_off"], np.int64), np.asarray(recovered["new_edge_off"], np.int64)
+    n_graphs = len(vertex_off) - 1
+    if pruned is None:
+        va, ea = np.zeros(vertex_off[-1], np.uint8), np.zeros(edge_off[-1], np.uint8)
+    elif "vertex_state" in pruned:
+        va, ea = ((np.asarray(pruned["vertex_state"]) & _GONE) != 0).astype(np.uint8), ((np.asarray(pruned["edge_state"]) & _GONE) != 0).astype(np.uint8)
+    else:
+        va, ea = np.asarray(pruned["vertex_absent"], np.uint8).copy(), np.asarray(pruned["edge_absent"], np.uint8).copy()
+    ea = ea | (np.asarray(recovered["edge_removed"], np.uint8) != 0)
+    new_gone = (np.asarray(recovered["new_edge_src"]) == 0xFFFFFFFF).astype(np.uint8)
+    cols = {"edge_src": (np.uint32, recovered["new_edge_src"]), "edge_dst": (np.uint32, recovered["new_edge_dst"]),
+            "edge_is_ref": (np.uint8, np.zeros(len(new_gone), np.uint8)), "edge_multiplicity": (np.uint32, recovered["new_edge_multiplicity"]),
+            "edge_pruning_multiplicity": (np.uint32, recovered["new_edge_pruning_multiplicity"]), "edge_absent": (np.uint8, new_gone)}
+    old = dict(graph, edge_absent=ea)
+    out = {name: [] for name in cols}
+    out["vertex_absent"] = []
+    for g in range(n_graphs):
+        e0, e1, n0, n1 = edge_off[g], edge_off[g + 1], ne_off[g], ne_off[g + 1]
+        for name, (dt, fresh) in cols.items():
+            out[name] += [np.asarray(old[name], dt).reshape(-1)[e0:e1], np.where(new_gone[n0:n1] != 0, 0, np.asarray(fresh, dt)[n0:n1]).astype(dt)
+                          if name in ("edge_src", "edge_dst") else np.asarray(fresh, dt)[n0:n1]]
+        out["vertex_absent"] += [va[vertex_off[g]:vertex_off[g + 1]], np.zeros(nv_off[g + 1] - nv_off[g], np.uint8)]
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
+    res = {name: cat(out[name], cols[name][0] if name in cols else np.uint8) for name in out}
+    res["vertex_off"] = (vertex_off + nv_off).astype(np.uint32)
+    res["edge_off"] = (edge_off + ne_off).astype(np.uint32)
+    res["new_vertex_kmer"], res["new_vertex_off"] = recovered["new_vertex_kmer"], np.asarray(recovered["new_vertex_off"], np.uint32)
+    if "k" in graph:
+        res["k"] = graph["k"]
+    return res

@@ -161,6 +161,7 @@ struct phmm_handle {
     StagingBuffer af_staging, annotate_staging, assign_staging, events_staging, activity_staging, finalize_staging, phase_staging, asm_staging, trim_staging;
     StagingBuffer graph_staging;  // phmm_assembly_graph (phmm_graph.cpp): its second half, sized once the graphs' sizes are known
     StagingBuffer prune_staging;  // phmm_assembly_prune (phmm_prune.cpp)
+    StagingBuffer recover_staging;  // phmm_assembly_recover (phmm_recover.cpp)
     // phmm_assembly_regions (phmm_regions.cpp): per state and read, per region, per membership -- each sized once its count is known
     StagingBuffer regions_staging, regions_out_staging, regions_reads_staging;
     // phmm_discover_events' device-only workspace (phmm_events.cpp), which phmm_trim_regions (phmm_trim.cpp) shares: grow-only, no host mirror
@@ -176,6 +177,8 @@ struct phmm_handle {
     size_t asm_scratch_cap = 0;
     char *prune_scratch = nullptr;  // phmm_assembly_prune: degrees, marks and chain pointers, 20 bytes per vertex and 5 per edge, device only
     size_t prune_scratch_cap = 0;
+    char *recover_scratch = nullptr;  // phmm_assembly_recover: the working graphs (41 bytes per vertex slot, 17 per edge slot) and the aligner's slabs, device only
+    size_t recover_scratch_cap = 0;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit
