@@ -41,13 +41,6 @@ bool band_kernel(uint32_t max_filter_size, double sigma, bool adaptive, uint32_t
     return !kernel->empty();
 }
 
-struct Out {  // an output array: on the device always, copied back and handed over when the caller wants it
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-    bool wanted() const { return user != nullptr; }
-};
-
 }  // namespace
 
 extern "C" {
@@ -224,9 +217,6 @@ int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples
         const auto s_nl = L.in(GT.neg_log10_alleles.data(), GT.neg_log10_alleles.size());
         L.end_inputs();
         const size_t n_ps = (size_t)n_pos * n_samples, n_list = (size_t)n_pos + (size_t)n_profiles * max_filter_size;
-        Out outs[12] = {{read_counts, 4 * n_ps},  {ref_depth, 4 * n_ps},      {non_ref_depth, 4 * n_ps}, {gl, 8 * n_ps * G},   {pl, 4 * n_ps * G},
-                        {soft_clip_mean, 8ull * n_pos}, {soft_clip_count, 4ull * n_pos}, {qual, 8ull * n_pos},  {af_flags, 4ull * n_pos}, {is_active_prob, 4ull * n_pos},
-                        {profile_prob, 4 * n_list}, {profile_len, 4ull * n_profiles}};
         StageLayout D;  // the device-only workspace
         const auto w_sl = D.scratch<uint16_t>(n_reads ? slot_off[n_reads] : 0);
         const auto w_tb = D.scratch<uint32_t>(n_reads ? tab_off[n_reads] : 0);
@@ -241,25 +231,20 @@ int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples
         const auto w_it = D.scratch<uint32_t>(n_pos);
         const auto w_ml = D.scratch<int64_t>(2ull * n_pos);
         const auto w_af = D.scratch<uint8_t>(2ull * n_pos);
-        for (Out &o : outs) {
-            if (o.wanted()) o.off = L.out<char>(o.bytes).off;
-            else o.off = D.scratch<char>(o.bytes).off;
-        }
-        if (h->activity_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->activity_scratch) (void)hipFree(h->activity_scratch);
-            h->activity_scratch = nullptr;
-            h->activity_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(activity profile workspace)")) return PHMM_ERR_HIP;
-            h->activity_scratch = ws;
-            h->activity_scratch_cap = bytes;
-        }
+        // an output is on the device always: staged and handed over when the caller wants it, else in the workspace
+        const auto o_rc = out_or_scratch(L, D, read_counts, n_ps), o_rd = out_or_scratch(L, D, ref_depth, n_ps), o_nd = out_or_scratch(L, D, non_ref_depth, n_ps);
+        const auto o_gl = out_or_scratch(L, D, gl, n_ps * G);
+        const auto o_pl = out_or_scratch(L, D, pl, n_ps * G);
+        const auto o_sm = out_or_scratch(L, D, soft_clip_mean, n_pos);
+        const auto o_sn = out_or_scratch(L, D, soft_clip_count, n_pos);
+        const auto o_ql = out_or_scratch(L, D, qual, n_pos);
+        const auto o_fl = out_or_scratch(L, D, af_flags, n_pos);
+        const auto o_ap = out_or_scratch(L, D, (float *)is_active_prob, n_pos), o_pp = out_or_scratch(L, D, (float *)profile_prob, n_list);
+        const auto o_pn = out_or_scratch(L, D, profile_len, n_profiles);
+        if (!h->activity_scratch.reserve(h, D, "activity profile workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "activity profile staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const ws = h->activity_scratch;
-        auto out_ptr = [&](int i) -> void * { return (outs[i].wanted() ? W.dev : ws) + outs[i].off; };
+        const DeviceScratch &ws = h->activity_scratch;
 
         ActivityParams p{};
         p.n_windows = n_windows;
@@ -298,26 +283,26 @@ int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples
         p.term = W.dev_ptr(s_tm);
         p.prob_of_qual = W.dev_ptr(s_pq);
         p.taps = W.dev_ptr(s_tp);
-        p.ws_slot = (uint16_t *)(ws + w_sl.off);
-        p.ws_tab = (uint32_t *)(ws + w_tb.off);
-        p.read_softclips = (double *)(ws + w_sc.off);
-        p.mult = (uint32_t *)(ws + w_mu.off);
+        p.ws_slot = ws.ptr(w_sl);
+        p.ws_tab = ws.ptr(w_tb);
+        p.read_softclips = ws.ptr(w_sc);
+        p.mult = ws.ptr(w_mu);
         p.prof_window = W.dev_ptr(s_pw);
         p.prof_pos = W.dev_ptr(s_pp);
         p.prof_n = W.dev_ptr(s_pn);
         p.max_prof_n = max_prof_n;
-        p.read_counts = (uint32_t *)out_ptr(0);
-        p.ref_depth = (uint32_t *)out_ptr(1);
-        p.non_ref_depth = (uint32_t *)out_ptr(2);
-        p.gl = (double *)out_ptr(3);
-        p.pl = (int32_t *)out_ptr(4);
-        p.softclip_mean = (double *)out_ptr(5);
-        p.softclip_count = (uint32_t *)out_ptr(6);
-        p.qual = (double *)out_ptr(7);
-        p.af_flags = (uint32_t *)out_ptr(8);
-        p.is_active_prob = (float *)out_ptr(9);
-        p.profile_prob = (float *)out_ptr(10);
-        p.profile_len = (uint32_t *)out_ptr(11);
+        p.read_counts = o_rc.dev_ptr(W, ws);
+        p.ref_depth = o_rd.dev_ptr(W, ws);
+        p.non_ref_depth = o_nd.dev_ptr(W, ws);
+        p.gl = o_gl.dev_ptr(W, ws);
+        p.pl = o_pl.dev_ptr(W, ws);
+        p.softclip_mean = o_sm.dev_ptr(W, ws);
+        p.softclip_count = o_sn.dev_ptr(W, ws);
+        p.qual = o_ql.dev_ptr(W, ws);
+        p.af_flags = o_fl.dev_ptr(W, ws);
+        p.is_active_prob = o_ap.dev_ptr(W, ws);
+        p.profile_prob = o_pp.dev_ptr(W, ws);
+        p.profile_len = o_pn.dev_ptr(W, ws);
 
         // the allele-frequency kernel on the PLs where they lie: one event per position, all of one shape
         AfParams a{};
@@ -325,11 +310,11 @@ int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples
         const bool block = af_is_block_event(G, n_samples);
         a.n_wave_events = block ? 0 : n_pos;
         a.n_block_events = block ? n_pos : 0;
-        uint32_t *const e_work = (uint32_t *)(ws + w_wk.off), *const e_allele_off = (uint32_t *)(ws + w_ao.off), *const e_count = (uint32_t *)(ws + w_gn.off);
-        int32_t *const e_span_del = (int32_t *)(ws + w_sd.off);
-        uint64_t *const e_pl_off = (uint64_t *)(ws + w_pl.off);
-        double *const e_prior = (double *)(ws + w_pr.off);
-        uint8_t *const e_kind = (uint8_t *)(ws + w_kd.off);
+        uint32_t *const e_work = ws.ptr(w_wk), *const e_allele_off = ws.ptr(w_ao), *const e_count = ws.ptr(w_gn);
+        int32_t *const e_span_del = ws.ptr(w_sd);
+        uint64_t *const e_pl_off = ws.ptr(w_pl);
+        double *const e_prior = ws.ptr(w_pr);
+        uint8_t *const e_kind = ws.ptr(w_kd);
         a.work = e_work;
         a.allele_off = e_allele_off;
         a.genotype_count = e_count;
@@ -347,27 +332,22 @@ int phmm_activity_profile(phmm_handle *h, uint32_t n_windows, uint32_t n_samples
         a.log_10 = std::log(10.0);
         a.inv_log_10 = 1.0 / a.log_10;
         a.log1mexp_threshold = std::log(0.5);
-        a.log10_p_no_variant = (double *)(ws + w_nv.off);
-        a.log10_p_variant_present = (double *)(ws + w_vp.off);
+        a.log10_p_no_variant = ws.ptr(w_nv);
+        a.log10_p_variant_present = ws.ptr(w_vp);
         a.qual = p.qual;
         a.flags = p.af_flags;
-        a.iterations = (uint32_t *)(ws + w_it.off);
-        a.log10_p_absent = (double *)(ws + w_ab.off);
-        a.mle_count = (int64_t *)(ws + w_ml.off);
-        a.allele_flags = (uint8_t *)(ws + w_af.off);
+        a.iterations = ws.ptr(w_it);
+        a.log10_p_absent = ws.ptr(w_ab);
+        a.mle_count = ws.ptr(w_ml);
+        a.allele_flags = ws.ptr(w_af);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D activity profile") ||
-            !hip_ok(h, launch_activity_pileup(p, S), "activity_read_kernel / activity_site_kernel") ||
-            !hip_ok(h, launch_activity_events(p, e_work, e_allele_off, e_count, e_span_del, e_pl_off, e_prior, e_kind, S), "activity_events_kernel") ||
-            !hip_ok(h, n_pos ? launch_af(a, af_genotypes_per_lane(G), S) : hipSuccess, "phmm_af_kernel") ||
-            !hip_ok(h, launch_activity_bandpass(p, S), "activity_bandpass_kernel"))
-            return PHMM_ERR_HIP;
-        if (L.total > L.out_begin && L.out_begin >= L.in_bytes &&
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H activity profile"))
-            return PHMM_ERR_HIP;
-        if (!hip_ok(h, hipStreamSynchronize(S), "sync(activity profile)")) return PHMM_ERR_HIP;
-        for (const Out &o : outs)
-            if (o.wanted() && o.bytes) memcpy(o.user, W.host + o.off, o.bytes);
+        const auto launch = [&] {
+            return hip_ok(h, launch_activity_pileup(p, S), "activity_read_kernel / activity_site_kernel") &&
+                   hip_ok(h, launch_activity_events(p, e_work, e_allele_off, e_count, e_span_del, e_pl_off, e_prior, e_kind, S), "activity_events_kernel") &&
+                   hip_ok(h, n_pos ? launch_af(a, af_genotypes_per_lane(G), S) : hipSuccess, "phmm_af_kernel") &&
+                   hip_ok(h, launch_activity_bandpass(p, S), "activity_bandpass_kernel");
+        };
+        if (!stage_round_trip(h, W, L, S, "activity profile", launch)) return PHMM_ERR_HIP;
         memcpy(window_status, status.data(), 4 * (size_t)n_windows);
         if (filter_size) *filter_size = F;
         return PHMM_OK;

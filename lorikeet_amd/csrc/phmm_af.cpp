@@ -222,16 +222,14 @@ int phmm_allele_frequency(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
         p.log10_p_absent = W.dev_ptr(s_abs);
         p.mle_count = W.dev_ptr(s_mle);
         p.allele_flags = W.dev_ptr(s_af);
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D allele frequency")) return PHMM_ERR_HIP;
+        if (!stage_upload(h, W, L, S, "allele frequency")) return PHMM_ERR_HIP;
         for (int c = 0; c < 4; ++c) {
             p.work = W.dev_ptr(s_wk) + cls_off[c][0];
             p.n_wave_events = cls_off[c][1];
             p.n_block_events = cls_off[c][2];
             if (!hip_ok(h, launch_af(p, classes[c], S), "phmm_af_kernel")) return PHMM_ERR_HIP;
         }
-        if (!hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H allele frequency") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(allele frequency)"))
-            return PHMM_ERR_HIP;
+        if (!stage_download(h, W, L, S, "allele frequency")) return PHMM_ERR_HIP;
         const double *r_pnv = W.host_ptr(s_pnv), *r_pvp = W.host_ptr(s_pvp), *r_q = W.host_ptr(s_q), *r_abs = W.host_ptr(s_abs);
         const uint32_t *r_fl = W.host_ptr(s_fl), *r_it = W.host_ptr(s_it);
         const int64_t *r_mle = W.host_ptr(s_mle);

@@ -204,11 +204,7 @@ int phmm_annotate_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
         p.qd_depth = W.dev_ptr(s_qdd);
         p.flags = W.dev_ptr(s_fl);
         p.mq = W.dev_ptr(s_mq);
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D annotate") ||
-            !hip_ok(h, launch_annotate(p, max_call, S), "phmm_annotate_kernel") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H annotate") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(annotate)"))
-            return PHMM_ERR_HIP;
+        if (!stage_round_trip(h, W, L, S, "annotate", [&] { return hip_ok(h, launch_annotate(p, max_call, S), "phmm_annotate_kernel"); })) return PHMM_ERR_HIP;
         // per allele and per (sample, allele) results go to the caller's call_allele_off offsets, the rest is dense
         for (uint32_t e = 0; e < n_events; ++e) {
             const size_t C = call_off[e + 1] - call_off[e], at = call_allele_off[e], from = call_off[e];

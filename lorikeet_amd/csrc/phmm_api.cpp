@@ -245,13 +245,7 @@ void phmm_destroy(phmm_handle *h) {
         if (h->arenas[i].rescue) (void)hipFree(h->arenas[i].rescue);
     }
     for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging, &h->events_staging, &h->activity_staging, &h->finalize_staging, &h->phase_staging, &h->asm_staging, &h->graph_staging, &h->prune_staging, &h->recover_staging, &h->trim_staging, &h->regions_staging, &h->regions_out_staging, &h->regions_reads_staging}) b->release();
-    if (h->events_scratch) (void)hipFree(h->events_scratch);
-    if (h->activity_scratch) (void)hipFree(h->activity_scratch);
-    if (h->finalize_scratch) (void)hipFree(h->finalize_scratch);
-    if (h->phase_scratch) (void)hipFree(h->phase_scratch);
-    if (h->asm_scratch) (void)hipFree(h->asm_scratch);
-    if (h->prune_scratch) (void)hipFree(h->prune_scratch);
-    if (h->recover_scratch) (void)hipFree(h->recover_scratch);
+    for (DeviceScratch *b : {&h->events_scratch, &h->activity_scratch, &h->finalize_scratch, &h->phase_scratch, &h->asm_scratch, &h->prune_scratch, &h->recover_scratch}) b->release();
     if (h->swork.slab) (void)hipFree(h->swork.slab);
     if (h->swork.ws) (void)hipFree(h->swork.ws);
     if (h->swork.ext) (void)hipFree(h->swork.ext);

@@ -11,16 +11,6 @@ using namespace phmm;
 
 using namespace phmm_host;
 
-namespace {
-
-struct Out {  // an output array the caller gave: where it lies in the staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
-}  // namespace
-
 namespace phmm {
 
 int asm_check(phmm_handle *h, const char *who, const AsmInputs &in, const AsmOutputsGiven &given, AsmBatch &b) {
@@ -116,40 +106,28 @@ AsmStaged asm_stage_inputs(StageLayout &L, const AsmInputs &in, const AsmBatch &
 AsmWorkspace asm_plan_workspace(StageLayout &D, const AsmBatch &b, size_t nk) {
     const size_t n_ref_bases = b.n_ref_bases, n_read_bases = b.n_read_bases, n_regions = b.n_regions, n_reads = b.n_reads, n_slots = b.n_slots;
     AsmWorkspace w;
-    w.fh = D.scratch<uint64_t>(n_ref_bases + n_regions).off;
-    w.dh = D.scratch<uint64_t>(n_read_bases + n_reads).off;
-    w.re = D.scratch<uint16_t>(n_read_bases).off;
-    w.ss = D.scratch<uint32_t>(nk * n_reads).off;
-    w.nr = D.scratch<uint32_t>(nk * n_reads).off;
-    w.fd = D.scratch<uint8_t>(nk * n_ref_bases).off;
-    w.dd = D.scratch<uint8_t>(nk * n_read_bases).off;
-    w.st = D.scratch<uint32_t>(b.long_sequence ? nk * 2 * (n_ref_bases + n_read_bases) : 0).off;
-    w.sc = D.scratch<unsigned long long>(nk * n_slots).off;
-    w.sr = D.scratch<uint32_t>(nk * n_slots).off;
-    w.sb = D.scratch<uint32_t>(nk * n_slots).off;
-    w.si = D.scratch<uint32_t>(nk * n_slots).off;
-    w.fs = D.scratch<uint32_t>(nk * n_ref_bases).off;
-    w.ds = D.scratch<uint32_t>(nk * n_read_bases).off;
+    w.fh = D.scratch<uint64_t>(n_ref_bases + n_regions);
+    w.dh = D.scratch<uint64_t>(n_read_bases + n_reads);
+    w.re = D.scratch<uint16_t>(n_read_bases);
+    w.ss = D.scratch<uint32_t>(nk * n_reads);
+    w.nr = D.scratch<uint32_t>(nk * n_reads);
+    w.fd = D.scratch<uint8_t>(nk * n_ref_bases);
+    w.dd = D.scratch<uint8_t>(nk * n_read_bases);
+    w.st = D.scratch<uint32_t>(b.long_sequence ? nk * 2 * (n_ref_bases + n_read_bases) : 0);
+    w.sc = D.scratch<unsigned long long>(nk * n_slots);
+    w.sr = D.scratch<uint32_t>(nk * n_slots);
+    w.sb = D.scratch<uint32_t>(nk * n_slots);
+    w.si = D.scratch<uint32_t>(nk * n_slots);
+    w.fs = D.scratch<uint32_t>(nk * n_ref_bases);
+    w.ds = D.scratch<uint32_t>(nk * n_read_bases);
     return w;
 }
 
-bool asm_reserve_workspace(phmm_handle *h, const StageLayout &D) {
-    if (h->asm_scratch_cap >= D.total) return true;
-    for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-    if (h->asm_scratch) (void)hipFree(h->asm_scratch);
-    h->asm_scratch = nullptr;
-    h->asm_scratch_cap = 0;
-    const size_t bytes = D.total + D.total / 2;
-    char *ws = nullptr;
-    if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(assembly k-mer workspace)")) return false;
-    h->asm_scratch = ws;
-    h->asm_scratch_cap = bytes;
-    return true;
-}
+bool asm_reserve_workspace(phmm_handle *h, const StageLayout &D) { return h->asm_scratch.reserve(h, D, "assembly k-mer workspace"); }
 
 void asm_bind(AsmParams &p, phmm_handle *h, const AsmInputs &in, const AsmBatch &b, const AsmStaged &s, const AsmWorkspace &w) {
     const StagingBuffer &W = h->asm_staging;
-    char *const ws = h->asm_scratch;
+    const DeviceScratch &ws = h->asm_scratch;
     p.n_regions = b.n_regions;
     p.n_reads = b.n_reads;
     p.n_k = in.n_k;
@@ -175,20 +153,20 @@ void asm_bind(AsmParams &p, phmm_handle *h, const AsmInputs &in, const AsmBatch 
     p.ref_bases = W.dev_ptr(s.fb);
     p.read_bases = W.dev_ptr(s.db);
     p.read_quals = W.dev_ptr(s.dq);
-    p.ref_hash = (uint64_t *)(ws + w.fh);
-    p.read_hash = (uint64_t *)(ws + w.dh);
-    p.run_end = (uint16_t *)(ws + w.re);
-    p.read_scan_stop = (uint32_t *)(ws + w.ss);
-    p.read_n_runs = (uint32_t *)(ws + w.nr);
-    p.ref_dup = (uint8_t *)(ws + w.fd);
-    p.read_dup = (uint8_t *)(ws + w.dd);
-    p.seq_table = b.long_sequence ? (uint32_t *)(ws + w.st) : nullptr;
-    p.slot_claim = (unsigned long long *)(ws + w.sc);
-    p.slot_rep = (uint32_t *)(ws + w.sr);
-    p.slot_bits = (uint32_t *)(ws + w.sb);
-    p.slot_id = (uint32_t *)(ws + w.si);
-    p.ref_slot = (uint32_t *)(ws + w.fs);
-    p.read_slot = (uint32_t *)(ws + w.ds);
+    p.ref_hash = ws.ptr(w.fh);
+    p.read_hash = ws.ptr(w.dh);
+    p.run_end = ws.ptr(w.re);
+    p.read_scan_stop = ws.ptr(w.ss);
+    p.read_n_runs = ws.ptr(w.nr);
+    p.ref_dup = ws.ptr(w.fd);
+    p.read_dup = ws.ptr(w.dd);
+    p.seq_table = b.long_sequence ? ws.ptr(w.st) : nullptr;
+    p.slot_claim = ws.ptr(w.sc);
+    p.slot_rep = ws.ptr(w.sr);
+    p.slot_bits = ws.ptr(w.sb);
+    p.slot_id = ws.ptr(w.si);
+    p.ref_slot = ws.ptr(w.fs);
+    p.read_slot = ws.ptr(w.ds);
 }
 
 }  // namespace phmm
@@ -219,38 +197,30 @@ extern "C" int phmm_assembly_kmers(phmm_handle *h, uint32_t n_regions, const uin
         StageLayout L;
         const AsmStaged staged = asm_stage_inputs(L, in, b);
         L.end_inputs();
-        const size_t nk = n_k, per = 4 * nk * n_regions;
-        Out outs[9] = {{flags, per}, {n_sequences, per}, {n_non_unique, per}, {n_tracked, per}, {n_distinct, per},
-                       {ref_kmer_flags, nk * n_ref_bases}, {read_kmer_flags, nk * n_read_bases},
-                       {ref_kmer_id, ids ? 4 * nk * n_ref_bases : 0}, {read_kmer_id, ids ? 4 * nk * n_read_bases : 0}};
-        for (Out &o : outs) o.off = L.out<char>(o.bytes).off;
+        const size_t nk = n_k, per = nk * n_regions;
+        const auto o_fl = L.out(flags, per), o_ns = L.out(n_sequences, per), o_nu = L.out(n_non_unique, per), o_nt = L.out(n_tracked, per), o_nd = L.out(n_distinct, per);
+        const auto o_ff = L.out(ref_kmer_flags, nk * n_ref_bases), o_df = L.out(read_kmer_flags, nk * n_read_bases);
+        const auto o_fi = L.out(ref_kmer_id, ids ? nk * n_ref_bases : 0), o_di = L.out(read_kmer_id, ids ? nk * n_read_bases : 0);
         StageLayout D;  // the device-only workspace
         const AsmWorkspace ws = asm_plan_workspace(D, b, nk);
         if (!asm_reserve_workspace(h, D)) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "assembly k-mer staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        auto out_ptr = [&](int i) -> void * { return outs[i].bytes ? W.dev + outs[i].off : nullptr; };
 
         AsmParams p{};
         asm_bind(p, h, in, b, staged, ws);
-        p.flags = (uint32_t *)out_ptr(0);
-        p.n_sequences = (uint32_t *)out_ptr(1);
-        p.n_non_unique = (uint32_t *)out_ptr(2);
-        p.n_tracked = (uint32_t *)out_ptr(3);
-        p.n_distinct = (uint32_t *)out_ptr(4);
-        p.ref_flags = (uint8_t *)out_ptr(5);
-        p.read_flags = (uint8_t *)out_ptr(6);
-        p.ref_kmer_id = (uint32_t *)out_ptr(7);
-        p.read_kmer_id = (uint32_t *)out_ptr(8);
+        p.flags = W.dev_ptr_or_null(o_fl);
+        p.n_sequences = W.dev_ptr_or_null(o_ns);
+        p.n_non_unique = W.dev_ptr_or_null(o_nu);
+        p.n_tracked = W.dev_ptr_or_null(o_nt);
+        p.n_distinct = W.dev_ptr_or_null(o_nd);
+        p.ref_flags = W.dev_ptr_or_null(o_ff);
+        p.read_flags = W.dev_ptr_or_null(o_df);
+        p.ref_kmer_id = W.dev_ptr_or_null(o_fi);
+        p.read_kmer_id = W.dev_ptr_or_null(o_di);
         p.want_ids = ids;   // (an empty plane's pointer is null and no kernel indexes it)
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D assembly k-mers") ||
-            !hip_ok(h, launch_assembly_kmers(p, S), "assembly k-mer kernels") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H assembly k-mers") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(assembly k-mers)"))
-            return PHMM_ERR_HIP;
-        for (const Out &o : outs)
-            if (o.bytes) memcpy(o.user, W.host + o.off, o.bytes);
+        if (!stage_round_trip(h, W, L, S, "assembly k-mers", [&] { return hip_ok(h, launch_assembly_kmers(p, S), "assembly k-mer kernels"); })) return PHMM_ERR_HIP;
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_assembly_kmers", PHMM_FAIL_CODE)
 }

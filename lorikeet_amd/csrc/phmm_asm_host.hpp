@@ -45,8 +45,12 @@ struct AsmStaged {  // the inputs in the staging buffer
     StageSlot<uint8_t> fb, db, dq;
 };
 
-struct AsmWorkspace {  // the device-only arrays, as offsets into the handle's workspace
-    size_t fh, dh, re, ss, nr, fd, dd, st, sc, sr, sb, si, fs, ds;
+struct AsmWorkspace {  // the device-only arrays in the handle's workspace
+    StageSlot<uint64_t> fh, dh;
+    StageSlot<uint16_t> re;
+    StageSlot<uint32_t> ss, nr, st, sr, sb, si, fs, ds;
+    StageSlot<uint8_t> fd, dd;
+    StageSlot<unsigned long long> sc;
 };
 
 // PHMM_OK with `b` filled (b.n_regions == 0: nothing to do), or PHMM_ERR_INVALID_ARG with "<who>: <first offender>" in the handle.

@@ -208,11 +208,7 @@ int phmm_assign_genotypes(phmm_handle *h, uint32_t n_events, uint32_t n_samples,
         p.flags = W.dev_ptr(s_fl);
         p.p_no_alt = W.dev_ptr(s_pna);
         p.qual_update = W.dev_ptr(s_qu);
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D genotype assignment") ||
-            !hip_ok(h, launch_assign(p, n_c, S), "phmm_assign_kernel") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H genotype assignment") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(genotype assignment)"))
-            return PHMM_ERR_HIP;
+        if (!stage_round_trip(h, W, L, S, "genotype assignment", [&] { return hip_ok(h, launch_assign(p, n_c, S), "phmm_assign_kernel"); })) return PHMM_ERR_HIP;
         for (uint32_t i = 0; i < n_c; ++i) {
             const uint32_t e = computed[i];
             const size_t n = (size_t)n_samples * c_Gn[i], from = c_out_off[i], es = (size_t)e * n_samples, is = (size_t)i * n_samples;

@@ -142,17 +142,7 @@ int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
         const auto o_hS = L.out<int64_t>(cap[4]), o_hE = L.out<int64_t>(cap[4]);
         const auto o_hr = L.out<uint32_t>(cap[4]), o_ho = L.out<uint32_t>(cap[4]), o_ht = L.out<uint32_t>(cap[4]);
         const auto o_hb = L.out<uint8_t>(cap[5]);
-        if (h->events_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->events_scratch) (void)hipFree(h->events_scratch);
-            h->events_scratch = nullptr;
-            h->events_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(event discovery workspace)")) return PHMM_ERR_HIP;
-            h->events_scratch = ws;
-            h->events_scratch_cap = bytes;
-        }
+        if (!h->events_scratch.reserve(h, D, "event discovery workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "event discovery staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
 
@@ -178,15 +168,15 @@ int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
         std::copy(cap, cap + 6, p.cap);
         p.max_loci = (uint32_t)max_loci;
         p.ws_ev_off = W.dev_ptr(s_sl);
-        p.ws_ev = (HapEvent *)(h->events_scratch + w_ev.off);
-        p.ws_alt = (uint8_t *)(h->events_scratch + w_al.off);
+        p.ws_ev = h->events_scratch.ptr(w_ev);
+        p.ws_alt = h->events_scratch.ptr(w_al);
         p.hap_n_ev = W.dev_ptr(w_ne);
         p.hap_n_alt = W.dev_ptr(w_na);
         p.hap_status = W.dev_ptr(w_hs);
         p.loci = W.dev_ptr(w_lo);
         p.region_n_loci = W.dev_ptr(w_nl);
         p.locus_base = W.dev_ptr(w_lb);
-        p.locus_cnt = (uint32_t *)(h->events_scratch + w_lc.off);
+        p.locus_cnt = h->events_scratch.ptr(w_lc);
         p.hap_dense_ev = maps ? W.dev_ptr(o_he) : W.dev_ptr(w_de);
         p.hap_dense_alt = W.dev_ptr(w_da);
         p.required = W.dev_ptr(o_rq);
@@ -211,11 +201,7 @@ int phmm_discover_events(phmm_handle *h, uint32_t n_regions, const uint32_t *reg
         p.hap_event_alt_off = W.dev_ptr(o_ho);
         p.hap_event_type = W.dev_ptr(o_ht);
         p.hap_event_alt = W.dev_ptr(o_hb);
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D event discovery") ||
-            !hip_ok(h, launch_events(p, S), "phmm_events kernels") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H event discovery") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(event discovery)"))
-            return PHMM_ERR_HIP;
+        if (!stage_round_trip(h, W, L, S, "event discovery", [&] { return hip_ok(h, launch_events(p, S), "phmm_events kernels"); })) return PHMM_ERR_HIP;
         const uint32_t *rq = W.host_ptr(o_rq);
         std::copy(rq, rq + 6, required);
         for (int k = 0; k < (maps ? 6 : 4); ++k)

@@ -19,13 +19,6 @@ int fail(phmm_handle *h, const std::string &msg) {
     return h->err_code = PHMM_ERR_INVALID_ARG;
 }
 
-struct Out {  // an output array: on the device always, copied back and handed over when the caller wants it
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-    bool wanted() const { return user != nullptr; }
-};
-
 constexpr int64_t kPosLimit = (int64_t)1 << 62;
 
 }  // namespace
@@ -126,33 +119,25 @@ extern "C" int phmm_finalize_reads(phmm_handle *h, const void *cfg_v, uint32_t n
         const auto s_mi = L.in(mate_index, mate_index ? n_reads : 0);
         const auto s_oo = L.in(cigar_room, (size_t)n_reads + 1);
         L.end_inputs();
-        Out outs[12] = {{read_status, 4ull * n_reads}, {keep, n_reads},           {new_pos, 8ull * n_reads},     {out_unmapped, n_reads},
-                        {clip_first, 4ull * n_reads},  {clip_len, 4ull * n_reads}, {out_cigar, 4 * n_out},        {n_out_cigar, 4ull * n_reads},
-                        {unclipped_len, 4ull * n_reads}, {lead_soft, 4ull * n_reads}, {trail_soft, 4ull * n_reads}, {out_quals, n_bases}};
         StageLayout D;  // the device-only workspace
         const auto w_cg = D.scratch<uint32_t>(2 * ((size_t)n_cigar + (size_t)n_reads * FIN_SLOT_EXTRA));
         const auto w_ps = D.scratch<int64_t>(n_reads);
         const auto w_fi = D.scratch<uint32_t>(n_reads), w_ln = D.scratch<uint32_t>(n_reads), w_nn = D.scratch<uint32_t>(n_reads);
         const auto w_fg = D.scratch<uint32_t>(n_reads), w_sl = D.scratch<uint32_t>(n_reads), w_sr = D.scratch<uint32_t>(n_reads);
-        for (Out &o : outs) {
-            if (o.wanted()) o.off = L.out<char>(o.bytes).off;
-            else o.off = D.scratch<char>(o.bytes).off;
-        }
-        if (h->finalize_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->finalize_scratch) (void)hipFree(h->finalize_scratch);
-            h->finalize_scratch = nullptr;
-            h->finalize_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(finalize workspace)")) return PHMM_ERR_HIP;
-            h->finalize_scratch = ws;
-            h->finalize_scratch_cap = bytes;
-        }
+        // an output is on the device always: staged and handed over when the caller wants it, else in the workspace
+        const auto o_st = out_or_scratch(L, D, read_status, n_reads);
+        const auto o_kp = out_or_scratch(L, D, keep, n_reads);
+        const auto o_np = out_or_scratch(L, D, new_pos, n_reads);
+        const auto o_um = out_or_scratch(L, D, out_unmapped, n_reads);
+        const auto o_cf = out_or_scratch(L, D, clip_first, n_reads), o_cl = out_or_scratch(L, D, clip_len, n_reads);
+        const auto o_cg = out_or_scratch(L, D, out_cigar, n_out, /*by_hand=*/true);
+        const auto o_nc = out_or_scratch(L, D, n_out_cigar, n_reads), o_ul = out_or_scratch(L, D, unclipped_len, n_reads);
+        const auto o_ls = out_or_scratch(L, D, lead_soft, n_reads), o_ts = out_or_scratch(L, D, trail_soft, n_reads);
+        const auto o_oq = out_or_scratch(L, D, out_quals, n_bases);
+        if (!h->finalize_scratch.reserve(h, D, "finalize workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "finalize staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const ws = h->finalize_scratch;
-        auto out_ptr = [&](int i) -> void * { return (outs[i].wanted() ? W.dev : ws) + outs[i].off; };
+        const DeviceScratch &ws = h->finalize_scratch;
 
         FinalizeParams p{};
         p.n_groups = n_groups;
@@ -177,48 +162,33 @@ extern "C" int phmm_finalize_reads(phmm_handle *h, const void *cfg_v, uint32_t n
         p.read_quals = W.dev_ptr(s_bq);
         p.mate_index = mate_index ? W.dev_ptr(s_mi) : nullptr;
         p.out_cigar_off = W.dev_ptr(s_oo);
-        p.ws_cigar = (uint32_t *)(ws + w_cg.off);
-        p.st_pos = (int64_t *)(ws + w_ps.off);
-        p.st_first = (uint32_t *)(ws + w_fi.off);
-        p.st_len = (uint32_t *)(ws + w_ln.off);
-        p.st_n = (uint32_t *)(ws + w_nn.off);
-        p.st_flags = (uint32_t *)(ws + w_fg.off);
-        p.scan_left = (uint32_t *)(ws + w_sl.off);
-        p.scan_right = (uint32_t *)(ws + w_sr.off);
-        p.status = (int32_t *)out_ptr(0);
-        p.keep = (uint8_t *)out_ptr(1);
-        p.new_pos = (int64_t *)out_ptr(2);
-        p.out_unmapped = (uint8_t *)out_ptr(3);
-        p.clip_first = (uint32_t *)out_ptr(4);
-        p.clip_len = (uint32_t *)out_ptr(5);
-        p.out_cigar = (uint32_t *)out_ptr(6);
-        p.n_out_cigar = (uint32_t *)out_ptr(7);
-        p.unclipped_len = (uint32_t *)out_ptr(8);
-        p.lead_soft = (uint32_t *)out_ptr(9);
-        p.trail_soft = (uint32_t *)out_ptr(10);
-        p.out_quals = (uint8_t *)out_ptr(11);
+        p.ws_cigar = ws.ptr(w_cg);
+        p.st_pos = ws.ptr(w_ps);
+        p.st_first = ws.ptr(w_fi);
+        p.st_len = ws.ptr(w_ln);
+        p.st_n = ws.ptr(w_nn);
+        p.st_flags = ws.ptr(w_fg);
+        p.scan_left = ws.ptr(w_sl);
+        p.scan_right = ws.ptr(w_sr);
+        p.status = o_st.dev_ptr(W, ws);
+        p.keep = o_kp.dev_ptr(W, ws);
+        p.new_pos = o_np.dev_ptr(W, ws);
+        p.out_unmapped = o_um.dev_ptr(W, ws);
+        p.clip_first = o_cf.dev_ptr(W, ws);
+        p.clip_len = o_cl.dev_ptr(W, ws);
+        p.out_cigar = o_cg.dev_ptr(W, ws);
+        p.n_out_cigar = o_nc.dev_ptr(W, ws);
+        p.unclipped_len = o_ul.dev_ptr(W, ws);
+        p.lead_soft = o_ls.dev_ptr(W, ws);
+        p.trail_soft = o_ts.dev_ptr(W, ws);
+        p.out_quals = o_oq.dev_ptr(W, ws);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D finalize") ||
-            !hip_ok(h, launch_finalize(p, S), "finalize kernels"))
-            return PHMM_ERR_HIP;
-        if (L.total > L.out_begin && L.out_begin >= L.in_bytes &&
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H finalize"))
-            return PHMM_ERR_HIP;
-        if (!hip_ok(h, hipStreamSynchronize(S), "sync(finalize)")) return PHMM_ERR_HIP;
+        if (!stage_round_trip(h, W, L, S, "finalize", [&] { return hip_ok(h, launch_finalize(p, S), "finalize kernels"); })) return PHMM_ERR_HIP;
         // out_cigar is copied read by read up to its count: the room between the reads stays as the caller left it
-        for (int i = 0; i < 12; ++i) {
-            const Out &o = outs[i];
-            if (!o.wanted() || !o.bytes) continue;
-            if (i == 6) {
-                const uint32_t *cg = (const uint32_t *)(W.host + o.off);
-                const uint32_t *cnt = (const uint32_t *)(W.host + outs[7].off);
-                for (uint32_t r = 0; r < n_reads; ++r) {
-                    const uint64_t n = cnt[r];
-                    if (n) memcpy(out_cigar + cigar_room[r], cg + cigar_room[r], 4 * n);
-                }
-            } else {
-                memcpy(o.user, W.host + o.off, o.bytes);
-            }
+        if (out_cigar) {
+            const uint32_t *cg = W.host_ptr(o_cg.slot), *cnt = W.host_ptr(o_nc.slot);
+            for (uint32_t r = 0; r < n_reads; ++r)
+                if (cnt[r]) memcpy(out_cigar + cigar_room[r], cg + cigar_room[r], 4ull * cnt[r]);
         }
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_finalize_reads", PHMM_FAIL_CODE)

@@ -218,11 +218,7 @@ int phmm_genotype_likelihoods(phmm_handle *h, uint32_t n_regions, const uint32_t
         p.gl = W.dev_ptr(s_gl);
         p.pl = W.dev_ptr(s_pl);
         p.n_evidence = W.dev_ptr(s_ne);
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D genotype") ||
-            !hip_ok(h, launch_genotype(p, S), "phmm_genotype_kernel") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H genotype") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(genotype)"))
-            return PHMM_ERR_HIP;
+        if (!stage_round_trip(h, W, L, S, "genotype", [&] { return hip_ok(h, launch_genotype(p, S), "phmm_genotype_kernel"); })) return PHMM_ERR_HIP;
         for (uint32_t e = 0; e < n_events; ++e) {
             const size_t n = (size_t)n_samples * G[e];
             memcpy(gl + gl_off[e], W.host_ptr(s_gl) + out_dense[e], 8 * n);

@@ -19,12 +19,6 @@ int fail(phmm_handle *h, const std::string &msg) {
     return h->err_code = PHMM_ERR_INVALID_ARG;
 }
 
-struct Out {  // an output array the caller gave: where it lies in the staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
 }  // namespace
 
 extern "C" int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
@@ -106,52 +100,50 @@ extern "C" int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uin
         if (!asm_reserve_workspace(h, D)) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "assembly graph staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const wsp = h->asm_scratch;
+        const DeviceScratch &wsp = h->asm_scratch;
 
         GraphParams p{};
         asm_bind(p.a, h, in, b, staged, ws);
-        uint32_t *const kc = (uint32_t *)(wsp + w_kc.off);
+        uint32_t *const kc = wsp.ptr(w_kc);
         p.a.flags = W.dev_ptr(o_fl);
         p.a.n_sequences = kc;
         p.a.n_non_unique = kc + n_graphs;
         p.a.n_tracked = kc + 2 * n_graphs;
         p.a.n_distinct = kc + 3 * n_graphs;
-        p.a.ref_flags = (uint8_t *)(wsp + w_ff.off);
-        p.a.read_flags = (uint8_t *)(wsp + w_df.off);
+        p.a.ref_flags = wsp.ptr(w_ff);
+        p.a.read_flags = wsp.ptr(w_df);
         p.a.want_ids = false;
         p.num_pruning_samples = num_pruning_samples;
         p.read_sample = W.dev_ptr(s_sm);
         p.region_n_samples = W.dev_ptr(s_ns);
-        p.read_rank = (uint32_t *)(wsp + w_rk.off);
-        p.read_group = (uint32_t *)(wsp + w_rg.off);
-        p.order = (uint32_t *)(wsp + w_or.off);
-        p.n_yield = (uint32_t *)(wsp + w_ny.off);
-        p.n_groups = (uint32_t *)(wsp + w_ng.off);
-        p.ref_handle = (uint32_t *)(wsp + w_fh.off);
-        p.read_handle = (uint32_t *)(wsp + w_dh.off);
-        p.ref_edge = (uint32_t *)(wsp + w_fe.off);
-        p.read_edge = (uint32_t *)(wsp + w_de.off);
-        p.trie_claim = (unsigned long long *)(wsp + w_tc.off);
-        p.v_stamp = (unsigned long long *)(wsp + w_vs.off);
-        p.v_in1 = (unsigned long long *)(wsp + w_v1.off);
-        p.v_in2 = (unsigned long long *)(wsp + w_v2.off);
-        p.v_inedge = (uint32_t *)(wsp + w_ve.off);
-        p.v_index = (uint32_t *)(wsp + w_vi.off);
-        p.e_key = (unsigned long long *)(wsp + w_ek.off);
-        p.e_stamp = (unsigned long long *)(wsp + w_es.off);
-        p.e_index = (uint32_t *)(wsp + w_ei.off);
-        p.seq_n_vertices = (uint32_t *)(wsp + w_sv.off);
-        p.seq_n_edges = (uint32_t *)(wsp + w_se.off);
-        p.seq_vertex_base = (uint32_t *)(wsp + w_bv.off);
-        p.seq_edge_base = (uint32_t *)(wsp + w_be.off);
+        p.read_rank = wsp.ptr(w_rk);
+        p.read_group = wsp.ptr(w_rg);
+        p.order = wsp.ptr(w_or);
+        p.n_yield = wsp.ptr(w_ny);
+        p.n_groups = wsp.ptr(w_ng);
+        p.ref_handle = wsp.ptr(w_fh);
+        p.read_handle = wsp.ptr(w_dh);
+        p.ref_edge = wsp.ptr(w_fe);
+        p.read_edge = wsp.ptr(w_de);
+        p.trie_claim = wsp.ptr(w_tc);
+        p.v_stamp = wsp.ptr(w_vs);
+        p.v_in1 = wsp.ptr(w_v1);
+        p.v_in2 = wsp.ptr(w_v2);
+        p.v_inedge = wsp.ptr(w_ve);
+        p.v_index = wsp.ptr(w_vi);
+        p.e_key = wsp.ptr(w_ek);
+        p.e_stamp = wsp.ptr(w_es);
+        p.e_index = wsp.ptr(w_ei);
+        p.seq_n_vertices = wsp.ptr(w_sv);
+        p.seq_n_edges = wsp.ptr(w_se);
+        p.seq_vertex_base = wsp.ptr(w_bv);
+        p.seq_edge_base = wsp.ptr(w_be);
         p.n_vertices = W.dev_ptr(o_nv);
         p.n_edges = W.dev_ptr(o_ne);
         p.n_ref_path = W.dev_ptr(o_np);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D assembly graph") ||
-            !hip_ok(h, launch_graph_build(p, S), "assembly graph kernels, first half") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H assembly graph sizes") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(assembly graph sizes)"))
+        if (!stage_upload(h, W, L, S, "assembly graph sizes") || !hip_ok(h, launch_graph_build(p, S), "assembly graph kernels, first half") ||
+            !stage_download(h, W, L, S, "assembly graph sizes"))
             return PHMM_ERR_HIP;
 
         // ---- the sizes: offsets, capacities ----------------------------------------------------------------------------------------
@@ -186,18 +178,15 @@ extern "C" int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uin
         const auto s_cw = M.in(width.data(), n_graphs);
         M.end_inputs();
         const auto w_ct = M.scratch<uint32_t>(n_counts), w_eg = M.scratch<uint32_t>(E);
-        Out outs[11] = {{vertex_seq, 4 * (size_t)V}, {vertex_pos, 4 * (size_t)V}, {vertex_flags, V}, {edge_src, 4 * (size_t)E}, {edge_dst, 4 * (size_t)E},
-                        {edge_is_ref, E}, {edge_multiplicity, 4 * (size_t)E}, {edge_pruning_multiplicity, 4 * (size_t)E}, {ref_path, 4 * (size_t)P},
-                        {ref_vertex, planes ? 4 * nk * n_ref_bases : 0}, {read_vertex, planes ? 4 * nk * n_read_bases : 0}};
-        bool any = false;
-        for (Out &o : outs) {
-            o.off = M.out<char>(o.bytes).off;
-            any |= o.bytes != 0;
-        }
-        if (any) {
+        const auto o_vq = M.out(vertex_seq, V), o_vp = M.out(vertex_pos, V);
+        const auto o_vf = M.out(vertex_flags, V);
+        const auto o_es = M.out(edge_src, E), o_ed = M.out(edge_dst, E);
+        const auto o_er = M.out(edge_is_ref, E);
+        const auto o_em = M.out(edge_multiplicity, E), o_ep = M.out(edge_pruning_multiplicity, E), o_rp = M.out(ref_path, P);
+        const auto o_fv = M.out(ref_vertex, planes ? nk * n_ref_bases : 0), o_dv = M.out(read_vertex, planes ? nk * n_read_bases : 0);
+        if (M.out_bytes()) {
             if (!G.reserve(h, M, "assembly graph outputs")) return PHMM_ERR_HIP;
             h->stat_staged_bytes += M.in_bytes;
-            auto out_ptr = [&](int i) -> void * { return outs[i].bytes ? G.dev + outs[i].off : nullptr; };
             p.vertex_off = G.dev_ptr(s_vo);
             p.edge_off = G.dev_ptr(s_eo);
             p.ref_path_off = G.dev_ptr(s_po);
@@ -207,25 +196,20 @@ extern "C" int phmm_assembly_graph(phmm_handle *h, uint32_t n_regions, const uin
             p.edge_group = G.dev_ptr(w_eg);
             p.n_counts = n_counts;
             p.max_edges = max_edges;
-            p.vertex_seq = (uint32_t *)out_ptr(0);
-            p.vertex_pos = (uint32_t *)out_ptr(1);
-            p.vertex_flags = (uint8_t *)out_ptr(2);
-            p.edge_src = (uint32_t *)out_ptr(3);
-            p.edge_dst = (uint32_t *)out_ptr(4);
-            p.edge_is_ref = (uint8_t *)out_ptr(5);
-            p.edge_multiplicity = (uint32_t *)out_ptr(6);
-            p.edge_pruning_multiplicity = (uint32_t *)out_ptr(7);
-            p.ref_path = (uint32_t *)out_ptr(8);
-            p.ref_vertex = planes ? (uint32_t *)out_ptr(9) : nullptr;
-            p.read_vertex = planes ? (uint32_t *)out_ptr(10) : nullptr;
+            p.vertex_seq = G.dev_ptr_or_null(o_vq);
+            p.vertex_pos = G.dev_ptr_or_null(o_vp);
+            p.vertex_flags = G.dev_ptr_or_null(o_vf);
+            p.edge_src = G.dev_ptr_or_null(o_es);
+            p.edge_dst = G.dev_ptr_or_null(o_ed);
+            p.edge_is_ref = G.dev_ptr_or_null(o_er);
+            p.edge_multiplicity = G.dev_ptr_or_null(o_em);
+            p.edge_pruning_multiplicity = G.dev_ptr_or_null(o_ep);
+            p.ref_path = G.dev_ptr_or_null(o_rp);
+            p.ref_vertex = G.dev_ptr_or_null(o_fv);
+            p.read_vertex = G.dev_ptr_or_null(o_dv);
             p.want_planes = planes;
-            if (!hip_ok(h, hipMemcpyAsync(G.dev, G.host, M.in_bytes, hipMemcpyHostToDevice, S), "H2D assembly graph offsets") ||
-                !hip_ok(h, launch_graph_fill(p, S), "assembly graph kernels, second half") ||
-                !hip_ok(h, hipMemcpyAsync(G.host + M.out_begin, G.dev + M.out_begin, M.total - M.out_begin, hipMemcpyDeviceToHost, S), "D2H assembly graph") ||
-                !hip_ok(h, hipStreamSynchronize(S), "sync(assembly graph)"))
+            if (!stage_round_trip(h, G, M, S, "assembly graph", [&] { return hip_ok(h, launch_graph_fill(p, S), "assembly graph kernels, second half"); }))
                 return PHMM_ERR_HIP;
-            for (const Out &o : outs)
-                if (o.bytes) memcpy(o.user, G.host + o.off, o.bytes);
         }
         memcpy(required, need, sizeof need);
         memcpy(flags, W.host_ptr(o_fl), 4 * n_graphs);

@@ -49,8 +49,24 @@ struct StagingBuffer {
         return (T *)(dev + s.off);
     }
     template <class T>
+    T *dev_ptr_or_null(StageSlot<T> s) const {  // for the kernels that take null for an array of no elements
+        return s.count ? dev_ptr(s) : nullptr;
+    }
+    template <class T>
     T *host_ptr(StageSlot<T> s) const {
         return (T *)(host + s.off);
+    }
+};
+// Grow-only device-only workspace of such an entry point: no mirror, never copied.  A call lays it out with a StageLayout of
+// scratch slots only (the member functions are in phmm_staging.hpp too).
+struct DeviceScratch {
+    char *dev = nullptr;
+    size_t cap = 0;
+    bool reserve(phmm_handle *h, const phmm_host::StageLayout &D, const char *owner);
+    void release();  // (phmm_destroy)
+    template <class T>
+    T *ptr(StageSlot<T> s) const {
+        return (T *)(dev + s.off);
     }
 };
 
@@ -164,21 +180,14 @@ struct phmm_handle {
     StagingBuffer recover_staging;  // phmm_assembly_recover (phmm_recover.cpp)
     // phmm_assembly_regions (phmm_regions.cpp): per state and read, per region, per membership -- each sized once its count is known
     StagingBuffer regions_staging, regions_out_staging, regions_reads_staging;
-    // phmm_discover_events' device-only workspace (phmm_events.cpp), which phmm_trim_regions (phmm_trim.cpp) shares: grow-only, no host mirror
-    char *events_scratch = nullptr;
-    size_t events_scratch_cap = 0;
-    char *activity_scratch = nullptr;  // phmm_activity_profile: the reads' slots and position tables, the event list, device only
-    size_t activity_scratch_cap = 0;
-    char *finalize_scratch = nullptr;  // phmm_finalize_reads: the reads' CIGAR slots and what the soft-clip step left of them, device only
-    size_t finalize_scratch_cap = 0;
-    char *phase_scratch = nullptr;  // phmm_phase_calls: the haplotype bitsets of the regions and of the calls, device only
-    size_t phase_scratch_cap = 0;
-    char *asm_scratch = nullptr;  // phmm_assembly_kmers: prefix hashes, runs, the sequences' and the regions' k-mer tables, device only
-    size_t asm_scratch_cap = 0;
-    char *prune_scratch = nullptr;  // phmm_assembly_prune: degrees, marks and chain pointers, 20 bytes per vertex and 5 per edge, device only
-    size_t prune_scratch_cap = 0;
-    char *recover_scratch = nullptr;  // phmm_assembly_recover: the working graphs (41 bytes per vertex slot, 17 per edge slot) and the aligner's slabs, device only
-    size_t recover_scratch_cap = 0;
+    // the device-only workspaces of the same entry points
+    DeviceScratch events_scratch;    // phmm_discover_events (phmm_events.cpp), which phmm_trim_regions (phmm_trim.cpp) shares
+    DeviceScratch activity_scratch;  // phmm_activity_profile: the reads' slots and position tables, the event list
+    DeviceScratch finalize_scratch;  // phmm_finalize_reads: the reads' CIGAR slots and what the soft-clip step left of them
+    DeviceScratch phase_scratch;     // phmm_phase_calls: the haplotype bitsets of the regions and of the calls
+    DeviceScratch asm_scratch;       // phmm_assembly_kmers: prefix hashes, runs, the sequences' and the regions' k-mer tables; phmm_assembly_graph shares it
+    DeviceScratch prune_scratch;     // phmm_assembly_prune: degrees, marks and chain pointers, 20 bytes per vertex and 5 per edge
+    DeviceScratch recover_scratch;   // phmm_assembly_recover: the working graphs (41 bytes per vertex slot, 17 per edge slot) and the aligner's slabs
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

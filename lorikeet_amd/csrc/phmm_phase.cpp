@@ -19,12 +19,6 @@ int fail(phmm_handle *h, const std::string &msg) {
     return h->err_code = PHMM_ERR_INVALID_ARG;
 }
 
-struct Out {  // an output array the caller gave: where it lies in the staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
 }  // namespace
 
 extern "C" int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32_t *region_event_off, const uint32_t *region_hap_off,
@@ -159,31 +153,25 @@ extern "C" int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32
         const auto s_co = L.in(call_allele_off, n_events ? (size_t)n_events + 1 : 0), s_ca = L.in(call_allele, n_call);
         const auto s_gt = L.in(gt, n_gt * ploidy);
         L.end_inputs();
-        Out outs[12] = {{call_rev_trim, 4ull * n_events}, {call_end, 8ull * n_events},    {phase_n_haps, 4ull * n_events},
-                        {hap_in_call, hap_in_call && n_events ? n_map : 0},               {phase_group, 4ull * n_events},
-                        {phase_gt, n_events},             {phase_leader, 4ull * n_events}, {phase_set, 8ull * n_events},
-                        {region_alt_haps, 4ull * n_regions}, {region_phase_flags, 4ull * n_regions},
-                        {is_phased, n_gt},                {gt_phased, 4 * n_gt * ploidy}};
-        for (Out &o : outs) o.off = L.out<char>(o.bytes).off;
+        const auto o_rt = L.out(call_rev_trim, n_events);
+        const auto o_ce = L.out(call_end, n_events);
+        const auto o_nh = L.out(phase_n_haps, n_events);
+        const auto o_hc = L.out(hap_in_call, hap_in_call && n_events ? n_map : 0);  // (not given: no slot, and the kernels see null)
+        const auto o_pg = L.out(phase_group, n_events);
+        const auto o_pt = L.out(phase_gt, n_events);
+        const auto o_pl = L.out(phase_leader, n_events);
+        const auto o_ps = L.out(phase_set, n_events);
+        const auto o_ah = L.out(region_alt_haps, n_regions), o_pf = L.out(region_phase_flags, n_regions);
+        const auto o_ip = L.out(is_phased, n_gt);
+        const auto o_gp = L.out(gt_phased, n_gt * ploidy);
         StageLayout D;  // the device-only workspace
         const auto w_rc = D.scratch<unsigned long long>((size_t)n_regions * PH_WORDS);
         const auto w_st = D.scratch<unsigned long long>((size_t)n_events * PH_WORDS);
         const auto w_gl = D.scratch<uint32_t>(n_events);
-        if (h->phase_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->phase_scratch) (void)hipFree(h->phase_scratch);
-            h->phase_scratch = nullptr;
-            h->phase_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(phasing workspace)")) return PHMM_ERR_HIP;
-            h->phase_scratch = ws;
-            h->phase_scratch_cap = bytes;
-        }
+        if (!h->phase_scratch.reserve(h, D, "phasing workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "phasing staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const ws = h->phase_scratch;
-        auto out_ptr = [&](int i) -> void * { return outs[i].bytes ? W.dev + outs[i].off : nullptr; };
+        const DeviceScratch &ws = h->phase_scratch;
 
         PhaseParams p{};
         p.n_regions = n_regions;
@@ -209,31 +197,25 @@ extern "C" int phmm_phase_calls(phmm_handle *h, uint32_t n_regions, const uint32
         p.call_allele_off = W.dev_ptr(s_co);
         p.call_allele = W.dev_ptr(s_ca);
         p.gt = gt ? W.dev_ptr(s_gt) : nullptr;
-        p.region_called = (unsigned long long *)(ws + w_rc.off);
-        p.sets = (unsigned long long *)(ws + w_st.off);
-        p.group_leader = (uint32_t *)(ws + w_gl.off);
-        p.call_rev_trim = (uint32_t *)out_ptr(0);
-        p.call_end = (int64_t *)out_ptr(1);
-        p.phase_n_haps = (uint32_t *)out_ptr(2);
-        p.hap_in_call = (uint8_t *)out_ptr(3);
-        p.phase_group = (int32_t *)out_ptr(4);
-        p.phase_gt = (uint8_t *)out_ptr(5);
-        p.phase_leader = (int32_t *)out_ptr(6);
-        p.phase_set = (int64_t *)out_ptr(7);
-        p.region_alt_haps = (uint32_t *)out_ptr(8);
-        p.region_phase_flags = (uint32_t *)out_ptr(9);
-        p.is_phased = (uint8_t *)out_ptr(10);
-        p.gt_phased = (int32_t *)out_ptr(11);
+        p.region_called = ws.ptr(w_rc);
+        p.sets = ws.ptr(w_st);
+        p.group_leader = ws.ptr(w_gl);
+        p.call_rev_trim = W.dev_ptr_or_null(o_rt);
+        p.call_end = W.dev_ptr_or_null(o_ce);
+        p.phase_n_haps = W.dev_ptr_or_null(o_nh);
+        p.hap_in_call = W.dev_ptr_or_null(o_hc);
+        p.phase_group = W.dev_ptr_or_null(o_pg);
+        p.phase_gt = W.dev_ptr_or_null(o_pt);
+        p.phase_leader = W.dev_ptr_or_null(o_pl);
+        p.phase_set = W.dev_ptr_or_null(o_ps);
+        p.region_alt_haps = W.dev_ptr_or_null(o_ah);
+        p.region_phase_flags = W.dev_ptr_or_null(o_pf);
+        p.is_phased = W.dev_ptr_or_null(o_ip);
+        p.gt_phased = W.dev_ptr_or_null(o_gp);
         // gt with no sample or no event has nothing to write: the stage is skipped as without gt
         if (!n_gt) p.gt = nullptr;
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D phasing") ||
-            !hip_ok(h, launch_phase(p, S), "phasing kernels") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H phasing") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(phasing)"))
-            return PHMM_ERR_HIP;
-        for (const Out &o : outs)
-            if (o.bytes) memcpy(o.user, W.host + o.off, o.bytes);
+        if (!stage_round_trip(h, W, L, S, "phasing", [&] { return hip_ok(h, launch_phase(p, S), "phasing kernels"); })) return PHMM_ERR_HIP;
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_phase_calls", PHMM_FAIL_CODE)
 }

@@ -17,12 +17,6 @@ int fail(phmm_handle *h, const std::string &msg) {
     return h->err_code = PHMM_ERR_INVALID_ARG;
 }
 
-struct Out {  // an output array: where it lies in the staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
 }  // namespace
 
 extern "C" int phmm_assembly_prune(phmm_handle *h, uint32_t n_graphs, const uint32_t *vertex_off, const uint32_t *edge_off,
@@ -77,30 +71,18 @@ extern "C" int phmm_assembly_prune(phmm_handle *h, uint32_t n_graphs, const uint
         const auto s_va = L.in(vertex_absent, vertex_absent ? V : 0), s_ea = L.in(edge_absent, edge_absent ? E : 0);
         const auto s_pf = L.in(prune_factor, n_graphs);
         L.end_inputs();
-        Out outs[10] = {{graph_flags, 4ull * n_graphs},     {n_chains, 4ull * n_graphs},     {n_chains_removed, 4ull * n_graphs},
-                        {n_vertices_left, 4ull * n_graphs}, {n_edges_left, 4ull * n_graphs}, {ref_source, 4ull * n_graphs},
-                        {ref_sink, 4ull * n_graphs},        {edge_chain, 4ull * E},          {edge_state, E},
-                        {vertex_state, V}};
-        for (Out &o : outs) o.off = L.out<char>(o.bytes).off;
+        const auto o_gf = L.out(graph_flags, n_graphs), o_nc = L.out(n_chains, n_graphs), o_nr = L.out(n_chains_removed, n_graphs);
+        const auto o_vl = L.out(n_vertices_left, n_graphs), o_el = L.out(n_edges_left, n_graphs), o_so = L.out(ref_source, n_graphs);
+        const auto o_si = L.out(ref_sink, n_graphs), o_ec = L.out(edge_chain, E);
+        const auto o_es = L.out(edge_state, E), o_vs = L.out(vertex_state, V);
         StageLayout D;  // the device-only workspace: 20 bytes per vertex, 5 per edge
         const auto w_vi = D.scratch<uint32_t>(V), w_vu = D.scratch<uint32_t>(V), w_ve = D.scratch<uint32_t>(V), w_vr = D.scratch<uint32_t>(V), w_vm = D.scratch<uint32_t>(V);
         const auto w_ep = D.scratch<uint32_t>(E);
         const auto w_eb = D.scratch<uint8_t>(E);
-        if (h->prune_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->prune_scratch) (void)hipFree(h->prune_scratch);
-            h->prune_scratch = nullptr;
-            h->prune_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(pruning workspace)")) return PHMM_ERR_HIP;
-            h->prune_scratch = ws;
-            h->prune_scratch_cap = bytes;
-        }
+        if (!h->prune_scratch.reserve(h, D, "pruning workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "pruning staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const ws = h->prune_scratch;
-        auto out_ptr = [&](int i) -> void * { return outs[i].bytes ? W.dev + outs[i].off : nullptr; };
+        const DeviceScratch &ws = h->prune_scratch;
 
         PruneParams p{};
         p.n_graphs = n_graphs;
@@ -114,31 +96,25 @@ extern "C" int phmm_assembly_prune(phmm_handle *h, uint32_t n_graphs, const uint
         p.vertex_absent = vertex_absent ? W.dev_ptr(s_va) : nullptr;
         p.edge_absent = edge_absent ? W.dev_ptr(s_ea) : nullptr;
         p.prune_factor = W.dev_ptr(s_pf);
-        p.v_in = (uint32_t *)(ws + w_vi.off);
-        p.v_out = (uint32_t *)(ws + w_vu.off);
-        p.v_inedge = (uint32_t *)(ws + w_ve.off);
-        p.v_ref = (uint32_t *)(ws + w_vr.off);
-        p.v_mark = (uint32_t *)(ws + w_vm.off);
-        p.e_ptr = (uint32_t *)(ws + w_ep.off);
-        p.e_bits = (uint8_t *)(ws + w_eb.off);
-        p.graph_flags = (uint32_t *)out_ptr(0);
-        p.n_chains = (uint32_t *)out_ptr(1);
-        p.n_chains_removed = (uint32_t *)out_ptr(2);
-        p.n_vertices_left = (uint32_t *)out_ptr(3);
-        p.n_edges_left = (uint32_t *)out_ptr(4);
-        p.ref_source = (uint32_t *)out_ptr(5);
-        p.ref_sink = (uint32_t *)out_ptr(6);
-        p.edge_chain = (uint32_t *)out_ptr(7);
-        p.edge_state = (uint8_t *)out_ptr(8);
-        p.vertex_state = (uint8_t *)out_ptr(9);
+        p.v_in = ws.ptr(w_vi);
+        p.v_out = ws.ptr(w_vu);
+        p.v_inedge = ws.ptr(w_ve);
+        p.v_ref = ws.ptr(w_vr);
+        p.v_mark = ws.ptr(w_vm);
+        p.e_ptr = ws.ptr(w_ep);
+        p.e_bits = ws.ptr(w_eb);
+        p.graph_flags = W.dev_ptr_or_null(o_gf);
+        p.n_chains = W.dev_ptr_or_null(o_nc);
+        p.n_chains_removed = W.dev_ptr_or_null(o_nr);
+        p.n_vertices_left = W.dev_ptr_or_null(o_vl);
+        p.n_edges_left = W.dev_ptr_or_null(o_el);
+        p.ref_source = W.dev_ptr_or_null(o_so);
+        p.ref_sink = W.dev_ptr_or_null(o_si);
+        p.edge_chain = W.dev_ptr_or_null(o_ec);
+        p.edge_state = W.dev_ptr_or_null(o_es);
+        p.vertex_state = W.dev_ptr_or_null(o_vs);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D pruning") ||
-            !hip_ok(h, launch_prune(p, S), "pruning kernel") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H pruning") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(pruning)"))
-            return PHMM_ERR_HIP;
-        for (const Out &o : outs)
-            if (o.bytes) memcpy(o.user, W.host + o.off, o.bytes);
+        if (!stage_round_trip(h, W, L, S, "pruning", [&] { return hip_ok(h, launch_prune(p, S), "pruning kernel"); })) return PHMM_ERR_HIP;
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_assembly_prune", PHMM_FAIL_CODE)
 }

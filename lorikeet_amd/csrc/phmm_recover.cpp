@@ -202,20 +202,10 @@ extern "C" int phmm_assembly_recover(
         const auto w_es = D.scratch<uint32_t>(XE), w_ed = D.scratch<uint32_t>(XE), w_em = D.scratch<uint32_t>(XE), w_ep = D.scratch<uint32_t>(XE);
         const auto w_ef = D.scratch<uint8_t>(XE);
         const auto w_slab = D.scratch<unsigned char>(XEND ? slab_bytes * n_blocks : 0);
-        if (h->recover_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->recover_scratch) (void)hipFree(h->recover_scratch);
-            h->recover_scratch = nullptr;
-            h->recover_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(recovery workspace)")) return PHMM_ERR_HIP;
-            h->recover_scratch = ws;
-            h->recover_scratch_cap = bytes;
-        }
+        if (!h->recover_scratch.reserve(h, D, "recovery workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "recovery staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        char *const ws = h->recover_scratch;
+        const DeviceScratch &ws = h->recover_scratch;
 
         RecoverParams p{};
         p.n_graphs = n_graphs;
@@ -231,7 +221,7 @@ extern "C" int phmm_assembly_recover(
         p.k = W.dev_ptr(s_k);
         p.vertex_off = W.dev_ptr(s_vo);
         p.edge_off = W.dev_ptr(s_eo);
-        p.bases = (const uint8_t *)(W.dev + s_rb.off);
+        p.bases = W.dev_ptr(s_rb);
         p.vertex_base = W.dev_ptr(s_vb);
         p.edge_src = W.dev_ptr(s_es);
         p.edge_dst = W.dev_ptr(s_ed);
@@ -244,15 +234,15 @@ extern "C" int phmm_assembly_recover(
         p.xv_off = W.dev_ptr(s_xv);
         p.xe_off = W.dev_ptr(s_xe);
         p.xend_off = W.dev_ptr(s_xn);
-        p.xv = (uint32_t *)(ws + w_xv.off);
-        p.xv_absent = (uint8_t *)(ws + w_va.off);
-        p.xe_src = (uint32_t *)(ws + w_es.off);
-        p.xe_dst = (uint32_t *)(ws + w_ed.off);
-        p.xe_mult = (uint32_t *)(ws + w_em.off);
-        p.xe_pmult = (uint32_t *)(ws + w_ep.off);
-        p.xe_flags = (uint8_t *)(ws + w_ef.off);
+        p.xv = ws.ptr(w_xv);
+        p.xv_absent = ws.ptr(w_va);
+        p.xe_src = ws.ptr(w_es);
+        p.xe_dst = ws.ptr(w_ed);
+        p.xe_mult = ws.ptr(w_em);
+        p.xe_pmult = ws.ptr(w_ep);
+        p.xe_flags = ws.ptr(w_ef);
         p.xv_total = XV;
-        p.slab = (unsigned char *)(ws + w_slab.off);
+        p.slab = ws.ptr(w_slab);
         p.slab_stride = slab_bytes;
         p.slab_len = slab_len;
         p.g_counts = W.dev_ptr(o_counts);
@@ -272,12 +262,11 @@ extern "C" int phmm_assembly_recover(
         p.kmer_stride = k_max;
         p.edge_removed = W.dev_ptr(o_rm);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D recovery") ||
-            ((size_t)XNV * k_max && !hip_ok(h, hipMemsetAsync(W.dev + o_nk.off, 0, (size_t)XNV * k_max, S), "memset(new k-mers)")) ||
-            !hip_ok(h, launch_recover(p, n_blocks, S), "recovery kernel") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H recovery") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(recovery)"))
-            return PHMM_ERR_HIP;
+        const auto launch = [&] {
+            return (!o_nk.count || hip_ok(h, hipMemsetAsync(W.dev_ptr(o_nk), 0, o_nk.count, S), "memset(new k-mers)")) &&
+                   hip_ok(h, launch_recover(p, n_blocks, S), "recovery kernel");
+        };
+        if (!stage_round_trip(h, W, L, S, "recovery", launch)) return PHMM_ERR_HIP;
 
         // ---- the sizes; then, if everything fits, the slots cut down to what was made --------------------------------------------
         const uint32_t *counts = W.host_ptr(o_counts);

@@ -21,12 +21,6 @@ int fail(phmm_handle *h, const std::string &msg) {
     return h->err_code = PHMM_ERR_INVALID_ARG;
 }
 
-struct Out {  // an output array of the caller: where it lies in a staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
 }  // namespace
 
 extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32_t n_windows, uint32_t n_samples,
@@ -126,9 +120,9 @@ extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32
         const auto w_sf = LA.scratch<uint32_t>(n_states), w_sl = LA.scratch<uint32_t>(n_states), w_sg = LA.scratch<uint32_t>(n_states);
         const auto w_cn = LA.scratch<uint32_t>(n_profiles);
         const auto w_re = LA.scratch<int64_t>(n_reads), w_rm = LA.scratch<int64_t>(n_reads);
-        const auto o_st = LA.out<int32_t>(n_profiles);
-        const auto o_ro = LA.out<uint32_t>((size_t)n_profiles + 1);
-        const auto o_mq = LA.out<double>(n_reads);
+        const auto o_st = LA.out(profile_status, n_profiles);
+        const auto o_ro = LA.out(profile_region_off, (size_t)n_profiles + 1);
+        const auto o_mq = LA.out(read_mean_qual, n_reads);  // (fetched and handed over only if the caller asked for it)
         if (!A.reserve(h, LA, "assembly regions staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += LA.in_bytes;
 
@@ -173,10 +167,9 @@ extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32
         p.read_mean_qual = A.dev_ptr(o_mq);
 
         const size_t a_begin = o_st.off, a_bytes = o_ro.off + 4 * ((size_t)n_profiles + 1) - o_st.off;  // status and offsets
-        if (!hip_ok(h, hipMemcpyAsync(A.dev, A.host, LA.in_bytes, hipMemcpyHostToDevice, S), "H2D assembly regions") ||
+        if (!stage_upload(h, A, LA, S, "assembly regions, profiles") ||
             !hip_ok(h, launch_regions_cut(p, S), "regions_class_kernel / regions_cut_kernel / regions_scan_kernel") ||
-            !hip_ok(h, hipMemcpyAsync(A.host + a_begin, A.dev + a_begin, a_bytes, hipMemcpyDeviceToHost, S), "D2H assembly regions (profiles)") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(assembly regions, profiles)"))
+            !stage_fetch(h, A, a_begin, a_bytes, S, "assembly regions, profiles") || !stage_wait(h, S, "assembly regions, profiles"))
             return PHMM_ERR_HIP;
         const uint32_t R = A.host_ptr(o_ro)[n_profiles];  // <= n_states: every region drains a state
         const size_t n_pairs = reads ? (size_t)R * n_samples : 0;
@@ -188,10 +181,10 @@ extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32
         const auto w_f0 = LB.scratch<uint32_t>(R), w_rk = LB.scratch<uint32_t>(R);
         const auto w_lo = LB.scratch<uint32_t>(n_pairs), w_hi = LB.scratch<uint32_t>(n_pairs), w_pc = LB.scratch<uint32_t>(n_pairs);
         const auto o_nm = LB.out<uint64_t>(1);
-        const auto o_rs = LB.out<uint64_t>(R), o_rE = LB.out<uint64_t>(R), o_qs = LB.out<uint64_t>(R), o_qe = LB.out<uint64_t>(R);
-        const auto o_ns = LB.out<uint32_t>(R), o_fl = LB.out<uint32_t>(R);
-        const auto o_dn = LB.out<float>(R);
-        const auto o_nr = LB.out<uint32_t>(R);
+        const auto o_rs = LB.out(region_start, R), o_rE = LB.out(region_end, R), o_qs = LB.out(region_padded_start, R), o_qe = LB.out(region_padded_end, R);
+        const auto o_ns = LB.out(region_states, R), o_fl = LB.out(region_flags, R);
+        const auto o_dn = LB.out((float *)region_density, R);
+        const auto o_nr = LB.out(region_n_reads, R);
         const auto o_rr = LB.out<uint32_t>(reads ? n_pairs + 1 : 0);
         if (!B.reserve(h, LB, "assembly regions staging (regions)")) return PHMM_ERR_HIP;
         p.n_regions = R;
@@ -210,9 +203,7 @@ extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32
         p.region_density = B.dev_ptr(o_dn);
         p.region_n_reads = B.dev_ptr(o_nr);
         p.region_read_off = B.dev_ptr(o_rr);
-        if (!hip_ok(h, launch_regions_spans(p, S), "regions_span_kernel ... regions_finish_kernel") ||
-            !hip_ok(h, hipMemcpyAsync(B.host + LB.out_begin, B.dev + LB.out_begin, LB.total - LB.out_begin, hipMemcpyDeviceToHost, S), "D2H assembly regions (regions)") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(assembly regions, regions)"))
+        if (!hip_ok(h, launch_regions_spans(p, S), "regions_span_kernel ... regions_finish_kernel") || !stage_download(h, B, LB, S, "assembly regions, regions"))
             return PHMM_ERR_HIP;
         const uint64_t M = reads && R ? *B.host_ptr(o_nm) : 0;  // (without reads or regions no kernel writes it)
         if (M >> 32) return fail(h, "the regions' reads reach 2^32 entries");
@@ -227,33 +218,23 @@ extern "C" int phmm_assembly_regions(phmm_handle *h, uint32_t n_profiles, uint32
         StagingBuffer &Cb = h->regions_reads_staging;
         StageLayout LC;
         LC.end_inputs();
-        const auto o_rd = LC.out<uint32_t>(M);
+        const auto o_rd = LC.out(region_reads, M);
         if (M) {
             if (!Cb.reserve(h, LC, "assembly regions staging (reads)")) return PHMM_ERR_HIP;
             p.region_reads = Cb.dev_ptr(o_rd);
-            if (!hip_ok(h, launch_regions_members(p, S), "regions_members_kernel") ||
-                !hip_ok(h, hipMemcpyAsync(Cb.host, Cb.dev, 4 * (size_t)M, hipMemcpyDeviceToHost, S), "D2H assembly regions (reads)"))
+            if (!hip_ok(h, launch_regions_members(p, S), "regions_members_kernel") || !stage_fetch(h, Cb, o_rd.off, 4 * (size_t)M, S, "assembly regions, reads"))
                 return PHMM_ERR_HIP;
         }
-        if (n_reads && read_mean_qual &&
-            !hip_ok(h, hipMemcpyAsync(A.host + o_mq.off, A.dev + o_mq.off, 8 * (size_t)n_reads, hipMemcpyDeviceToHost, S), "D2H assembly regions (read_mean_qual)"))
-            return PHMM_ERR_HIP;
-        if (!hip_ok(h, hipStreamSynchronize(S), "sync(assembly regions)")) return PHMM_ERR_HIP;
+        if (n_reads && read_mean_qual && !stage_fetch(h, A, o_mq.off, 8 * (size_t)n_reads, S, "assembly regions, read_mean_qual")) return PHMM_ERR_HIP;
+        if (!stage_wait(h, S, "assembly regions")) return PHMM_ERR_HIP;
 
-        memcpy(profile_status, A.host_ptr(o_st), 4 * (size_t)n_profiles);
-        memcpy(profile_region_off, A.host_ptr(o_ro), 4 * ((size_t)n_profiles + 1));
-        if (n_reads && read_mean_qual) memcpy(read_mean_qual, A.host_ptr(o_mq), 8 * (size_t)n_reads);
-        const Out outs[8] = {{region_start, 8 * (size_t)R, o_rs.off},        {region_end, 8 * (size_t)R, o_rE.off},
-                             {region_padded_start, 8 * (size_t)R, o_qs.off}, {region_padded_end, 8 * (size_t)R, o_qe.off},
-                             {region_states, 4 * (size_t)R, o_ns.off},       {region_flags, 4 * (size_t)R, o_fl.off},
-                             {region_density, 4 * (size_t)R, o_dn.off},      {region_n_reads, 4 * (size_t)R, o_nr.off}};
-        for (const Out &o : outs)
-            if (o.bytes) memcpy(o.user, B.host + o.off, o.bytes);
+        LA.hand_over(A.host);
+        LB.hand_over(B.host);
         if (reads && region_read_off) {
             if (R) memcpy(region_read_off, B.host_ptr(o_rr), 4 * (n_pairs + 1));
             else region_read_off[0] = 0;
         }
-        if (M) memcpy(region_reads, Cb.host, 4 * (size_t)M);
+        LC.hand_over(Cb.host);
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_assembly_regions", PHMM_FAIL_CODE)
 }

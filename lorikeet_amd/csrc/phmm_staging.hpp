@@ -1,6 +1,6 @@
 // Private to the host side of libphmm.so: the small utilities every host file shares (device guard, HIP status, exception
-// guard), the grow-only staging buffer of the entry points that stage their arrays themselves, and the layout builder that
-// declares each staged array once.
+// guard), the grow-only staging buffer and device-only workspace of the entry points that stage their arrays themselves, the
+// layout builder that declares each staged array once, and the round trip of such a call.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -67,14 +67,21 @@ inline int on_exception(phmm_handle *h, const char *where, const char *what, int
 
 // Where the arrays of one call lie in a StagingBuffer: one statement per array gives its element type and count, in the order
 // [inputs | device-only scratch | results].  Every slot starts on a 256-byte boundary and a zero-count slot takes no room, so
-// one H2D copy covers [0, in_bytes) and one D2H copy [out_begin, total).
+// one H2D copy covers [0, in_bytes) and one D2H copy [out_begin, total).  A DeviceScratch is laid out the same way, with
+// scratch slots only.
 class StageLayout {
     struct Copy {
         size_t off;
         const void *src;
         size_t bytes;
     };
+    struct CopyBack {
+        size_t off;
+        void *dst;
+        size_t bytes;
+    };
     std::vector<Copy> copies;
+    std::vector<CopyBack> copy_backs;
     bool has_out = false;
     template <class T>
     StageSlot<T> place(size_t count) {
@@ -100,15 +107,67 @@ public:
         return place<T>(count);
     }
     template <class T>
-    StageSlot<T> out(size_t count) {
+    StageSlot<T> out(size_t count) {  // a result the caller cuts or scatters by hand (StagingBuffer::host_ptr)
         if (!has_out) out_begin = total;
         has_out = true;
         return place<T>(count);
     }
+    template <class T>
+    StageSlot<T> out(T *dst, size_t count) {  // copied from the mirror by hand_over(); a null dst is an array the caller did not ask for
+        const StageSlot<T> s = out<T>(count);
+        if (dst && count) copy_backs.push_back({s.off, dst, count * sizeof(T)});
+        return s;
+    }
+    size_t out_bytes() const { return has_out ? total - out_begin : 0; }  // what the D2H copy covers: 0 = there is none
     void stage(char *host) const {
         for (const Copy &c : copies) memcpy(host + c.off, c.src, c.bytes);
     }
+    void hand_over(const char *host) const {
+        for (const CopyBack &c : copy_backs) memcpy(c.dst, host + c.off, c.bytes);
+    }
 };
+
+// A result the kernels write whether or not the caller asked for it: in the staging layout L if `user` is given (handed over
+// like any L.out(user, count), or left to the caller's own copy with by_hand), else in the device-only workspace D.
+template <class T>
+struct OptionalOut {
+    StageSlot<T> slot;
+    bool staged;
+    T *dev_ptr(const StagingBuffer &W, const DeviceScratch &ws) const { return staged ? W.dev_ptr(slot) : ws.ptr(slot); }
+};
+template <class T>
+OptionalOut<T> out_or_scratch(StageLayout &L, StageLayout &D, T *user, size_t count, bool by_hand = false) {
+    if (!user) return {D.scratch<T>(count), false};
+    return {by_hand ? L.out<T>(count) : L.out(user, count), true};
+}
+
+// The round trip of a call on stream S, in pieces: the inputs of L to the device, any byte range of W back, the wait.  A HIP
+// failure leaves "<step> <what>" in the handle and returns false.
+inline bool stage_upload(phmm_handle *h, const StagingBuffer &W, const StageLayout &L, hipStream_t S, const char *what) {
+    const hipError_t e = hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S);
+    return e == hipSuccess || hip_ok(h, e, ("H2D " + std::string(what)).c_str());
+}
+inline bool stage_fetch(phmm_handle *h, const StagingBuffer &W, size_t begin, size_t bytes, hipStream_t S, const char *what) {
+    const hipError_t e = hipMemcpyAsync(W.host + begin, W.dev + begin, bytes, hipMemcpyDeviceToHost, S);
+    return e == hipSuccess || hip_ok(h, e, ("D2H " + std::string(what)).c_str());
+}
+inline bool stage_wait(phmm_handle *h, hipStream_t S, const char *what) {
+    const hipError_t e = hipStreamSynchronize(S);
+    return e == hipSuccess || hip_ok(h, e, ("sync(" + std::string(what) + ")").c_str());
+}
+// ... the results of L back, if it declared any, and the wait
+inline bool stage_download(phmm_handle *h, const StagingBuffer &W, const StageLayout &L, hipStream_t S, const char *what) {
+    if (L.out_bytes() && !stage_fetch(h, W, L.out_begin, L.out_bytes(), S, what)) return false;
+    return stage_wait(h, S, what);
+}
+// ... and the whole of it for a call of one round: upload, `launch` (which enqueues on S and returns false with the error set),
+// download, and every L.out(ptr, count) handed to the caller.  Nothing is handed over when a step fails.
+template <class Launch>
+bool stage_round_trip(phmm_handle *h, const StagingBuffer &W, const StageLayout &L, hipStream_t S, const char *what, Launch &&launch) {
+    if (!stage_upload(h, W, L, S, what) || !launch() || !stage_download(h, W, L, S, what)) return false;
+    L.hand_over(W.host);
+    return true;
+}
 
 // The likelihood matrices of the regions some event uses, one behind the other (phmm_genotype_likelihoods,
 // phmm_annotate_events): where each starts (0 for a region no event uses) and how many values they are together.
@@ -184,4 +243,24 @@ inline bool StagingBuffer::reserve(phmm_handle *h, const phmm_host::StageLayout 
     if (!grow(h, L.total, owner)) return false;
     L.stage(host);
     return true;
+}
+
+// Room for the layout D, one and a half times the need and no floor; growing waits for the handle's streams like
+// StagingBuffer::grow.  An empty layout on an empty workspace allocates nothing.
+inline bool DeviceScratch::reserve(phmm_handle *h, const phmm_host::StageLayout &D, const char *owner) {
+    if (cap >= D.total) return true;
+    for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
+    release();
+    const size_t bytes = D.total + D.total / 2;
+    if (!phmm_host::hip_ok(h, hipMalloc((void **)&dev, bytes), ("hipMalloc(" + std::string(owner) + ")").c_str())) {
+        dev = nullptr;
+        return false;
+    }
+    cap = bytes;
+    return true;
+}
+inline void DeviceScratch::release() {
+    if (dev) (void)hipFree(dev);
+    dev = nullptr;
+    cap = 0;
 }

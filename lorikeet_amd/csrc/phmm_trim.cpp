@@ -25,12 +25,6 @@ bool accepted(uint8_t b) {
     return b && strchr(ok, (int)b);
 }
 
-struct Out {  // an output array of the caller: where it lies in the staging buffer
-    void *user;
-    size_t bytes;
-    size_t off = 0;
-};
-
 }  // namespace
 
 extern "C" int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
@@ -133,34 +127,28 @@ extern "C" int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint3
         const auto w_hl = L.scratch<uint32_t>(n_haps), w_hr2 = L.scratch<uint32_t>(n_haps);
         const auto w_rn = L.scratch<uint32_t>(n_regions);
         const auto w_os = L.scratch<uint32_t>(n_haps), w_ol = L.scratch<uint32_t>(n_haps), w_oc = L.scratch<uint32_t>(n_haps);
-        const size_t R = n_regions, H = n_haps;
-        Out outs[21] = {{region_status, 4 * R}, {variation_present, R}, {variant_start, 8 * R}, {variant_end, 8 * R}, {padded_start, 8 * R},
-                        {padded_end, 8 * R}, {new_active_start, 8 * R}, {new_active_end, 8 * R}, {new_padded_start, 8 * R},
-                        {new_padded_end, 8 * R}, {hap_fate, 4 * H}, {hap_dup_of, 4 * H}, {out_region_hap_off, 4 * (R + 1)},
-                        {out_hap_off, 4 * (H + 1)}, {out_hap_bases, n_hap_bases}, {out_hap_cigar_off, 4 * (H + 1)},
-                        {out_hap_cigar, 4 * (size_t)n_cigar}, {out_hap_start_wrt_ref, 4 * H}, {out_hap_source, 4 * H}, {out_hap_is_ref, H},
-                        {out_region_ref_hap, 4 * R}};
-        for (Out &o : outs) o.off = L.out<char>(o.bytes).off;
+        const auto o_st = L.out(region_status, n_regions);
+        const auto o_vp = L.out(variation_present, n_regions);
+        const auto o_vs = L.out(variant_start, n_regions), o_ve = L.out(variant_end, n_regions), o_ps = L.out(padded_start, n_regions);
+        const auto o_pe = L.out(padded_end, n_regions), o_as = L.out(new_active_start, n_regions), o_ae = L.out(new_active_end, n_regions);
+        const auto o_qs = L.out(new_padded_start, n_regions), o_qe = L.out(new_padded_end, n_regions);
+        const auto o_hf = L.out(hap_fate, n_haps);
+        const auto o_hd = L.out(hap_dup_of, n_haps), o_rh = L.out(out_region_hap_off, (size_t)n_regions + 1);
+        // the dense arrays are cut by hand below: they are copied as far as they were written
+        const auto o_ho = L.out<uint32_t>((size_t)n_haps + 1);
+        const auto o_hb = L.out<uint8_t>(n_hap_bases);
+        const auto o_co = L.out<uint32_t>((size_t)n_haps + 1), o_cg = L.out<uint32_t>(n_cigar), o_hs = L.out<uint32_t>(n_haps), o_sr = L.out<uint32_t>(n_haps);
+        const auto o_ir = L.out<uint8_t>(n_haps);
+        const auto o_rr = L.out(out_region_ref_hap, n_regions);
         // The event slots are sized for the worst case and never copied: they lie in the device allocation phmm_discover_events
         // keeps, with the two CIGAR slots of every haplotype behind them.
         StageLayout D;
         const auto w_ev = D.scratch<HapEvent>(work);
         const auto w_al = D.scratch<uint8_t>(work);
         const auto w_ca = D.scratch<uint32_t>(n_cigar), w_cb = D.scratch<uint32_t>(n_cigar);
-        if (h->events_scratch_cap < D.total) {
-            for (int i = 0; i < kSlots; ++i) (void)hipStreamSynchronize(h->streams[i]);
-            if (h->events_scratch) (void)hipFree(h->events_scratch);
-            h->events_scratch = nullptr;
-            h->events_scratch_cap = 0;
-            const size_t bytes = D.total + D.total / 2;
-            char *ws = nullptr;
-            if (!hip_ok(h, hipMalloc((void **)&ws, bytes), "hipMalloc(region trimming workspace)")) return PHMM_ERR_HIP;
-            h->events_scratch = ws;
-            h->events_scratch_cap = bytes;
-        }
+        if (!h->events_scratch.reserve(h, D, "region trimming workspace")) return PHMM_ERR_HIP;
         if (!W.reserve(h, L, "region trimming staging")) return PHMM_ERR_HIP;
         h->stat_staged_bytes += L.in_bytes;
-        auto out_ptr = [&](int i) -> void * { return W.dev + outs[i].off; };
 
         EventsParams e{};
         e.n_regions = n_regions;
@@ -176,8 +164,8 @@ extern "C" int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint3
         e.hap_start = W.dev_ptr(s_hs);
         e.dist = max_mnp_distance;
         e.ws_ev_off = W.dev_ptr(s_sl);
-        e.ws_ev = (HapEvent *)(h->events_scratch + w_ev.off);
-        e.ws_alt = (uint8_t *)(h->events_scratch + w_al.off);
+        e.ws_ev = h->events_scratch.ptr(w_ev);
+        e.ws_alt = h->events_scratch.ptr(w_al);
         e.hap_n_ev = W.dev_ptr(w_ne);
         e.hap_n_alt = W.dev_ptr(w_na);
         e.hap_status = W.dev_ptr(w_hs);
@@ -212,51 +200,50 @@ extern "C" int phmm_trim_regions(phmm_handle *h, uint32_t n_regions, const uint3
         p.new_n_cigar = W.dev_ptr(w_nc);
         p.new_start = W.dev_ptr(w_ns);
         p.hap_panic = W.dev_ptr(w_hp);
-        p.ws_cigar_a = (uint32_t *)(h->events_scratch + w_ca.off);
-        p.ws_cigar_b = (uint32_t *)(h->events_scratch + w_cb.off);
+        p.ws_cigar_a = h->events_scratch.ptr(w_ca);
+        p.ws_cigar_b = h->events_scratch.ptr(w_cb);
         p.hap_below = W.dev_ptr(w_hl);
         p.hap_rep = W.dev_ptr(w_hr2);
         p.region_n_out = W.dev_ptr(w_rn);
         p.out_src = W.dev_ptr(w_os);
         p.out_len = W.dev_ptr(w_ol);
         p.out_n_cigar = W.dev_ptr(w_oc);
-        p.region_status = (int32_t *)out_ptr(0);
-        p.variation = (uint8_t *)out_ptr(1);
-        p.variant_start = (uint64_t *)out_ptr(2);
-        p.variant_end = (uint64_t *)out_ptr(3);
-        p.span_start = (uint64_t *)out_ptr(4);
-        p.span_end = (uint64_t *)out_ptr(5);
-        p.new_active_start = (uint64_t *)out_ptr(6);
-        p.new_active_end = (uint64_t *)out_ptr(7);
-        p.new_padded_start = (uint64_t *)out_ptr(8);
-        p.new_padded_end = (uint64_t *)out_ptr(9);
-        p.hap_fate = (int32_t *)out_ptr(10);
-        p.hap_dup_of = (uint32_t *)out_ptr(11);
-        p.out_region_hap_off = (uint32_t *)out_ptr(12);
-        p.out_hap_off = (uint32_t *)out_ptr(13);
-        p.out_bases = (uint8_t *)out_ptr(14);
-        p.out_cigar_off = (uint32_t *)out_ptr(15);
-        p.out_cigar = (uint32_t *)out_ptr(16);
-        p.out_start = (uint32_t *)out_ptr(17);
-        p.out_source = (uint32_t *)out_ptr(18);
-        p.out_is_ref = (uint8_t *)out_ptr(19);
-        p.out_region_ref_hap = (int32_t *)out_ptr(20);
+        p.region_status = W.dev_ptr(o_st);
+        p.variation = W.dev_ptr(o_vp);
+        p.variant_start = W.dev_ptr(o_vs);
+        p.variant_end = W.dev_ptr(o_ve);
+        p.span_start = W.dev_ptr(o_ps);
+        p.span_end = W.dev_ptr(o_pe);
+        p.new_active_start = W.dev_ptr(o_as);
+        p.new_active_end = W.dev_ptr(o_ae);
+        p.new_padded_start = W.dev_ptr(o_qs);
+        p.new_padded_end = W.dev_ptr(o_qe);
+        p.hap_fate = W.dev_ptr(o_hf);
+        p.hap_dup_of = W.dev_ptr(o_hd);
+        p.out_region_hap_off = W.dev_ptr(o_rh);
+        p.out_hap_off = W.dev_ptr(o_ho);
+        p.out_bases = W.dev_ptr(o_hb);
+        p.out_cigar_off = W.dev_ptr(o_co);
+        p.out_cigar = W.dev_ptr(o_cg);
+        p.out_start = W.dev_ptr(o_hs);
+        p.out_source = W.dev_ptr(o_sr);
+        p.out_is_ref = W.dev_ptr(o_ir);
+        p.out_region_ref_hap = W.dev_ptr(o_rr);
 
-        if (!hip_ok(h, hipMemcpyAsync(W.dev, W.host, L.in_bytes, hipMemcpyHostToDevice, S), "H2D region trimming") ||
-            !hip_ok(h, launch_trim(e, p, S), "phmm_trim kernels") ||
-            !hip_ok(h, hipMemcpyAsync(W.host + L.out_begin, W.dev + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, S), "D2H region trimming") ||
-            !hip_ok(h, hipStreamSynchronize(S), "sync(region trimming)"))
-            return PHMM_ERR_HIP;
-        // the dense arrays are copied as far as they were written: n_out haplotypes, their bases and elements
-        const uint32_t n_out = ((const uint32_t *)(W.host + outs[12].off))[n_regions];
-        const uint32_t n_out_bases = ((const uint32_t *)(W.host + outs[13].off))[n_out], n_out_cigar = ((const uint32_t *)(W.host + outs[15].off))[n_out];
-        outs[13].bytes = outs[15].bytes = 4 * ((size_t)n_out + 1);
-        outs[14].bytes = n_out_bases;
-        outs[16].bytes = 4 * (size_t)n_out_cigar;
-        outs[17].bytes = outs[18].bytes = 4 * (size_t)n_out;
-        outs[19].bytes = n_out;
-        for (const Out &o : outs)
-            if (o.bytes) memcpy(o.user, W.host + o.off, o.bytes);
+        if (!stage_round_trip(h, W, L, S, "region trimming", [&] { return hip_ok(h, launch_trim(e, p, S), "phmm_trim kernels"); })) return PHMM_ERR_HIP;
+        // the dense arrays: n_out haplotypes, their bases and elements
+        const uint32_t n_out = W.host_ptr(o_rh)[n_regions];
+        const uint32_t n_out_bases = W.host_ptr(o_ho)[n_out], n_out_cigar = W.host_ptr(o_co)[n_out];
+        const auto cut = [&](auto *dst, auto slot, size_t count) {
+            if (count) memcpy(dst, W.host_ptr(slot), count * sizeof *dst);
+        };
+        cut(out_hap_off, o_ho, (size_t)n_out + 1);
+        cut(out_hap_bases, o_hb, n_out_bases);
+        cut(out_hap_cigar_off, o_co, (size_t)n_out + 1);
+        cut(out_hap_cigar, o_cg, n_out_cigar);
+        cut(out_hap_start_wrt_ref, o_hs, n_out);
+        cut(out_hap_source, o_sr, n_out);
+        cut(out_hap_is_ref, o_ir, n_out);
         return PHMM_OK;
     PHMM_GUARD_END(h, "phmm_trim_regions", PHMM_FAIL_CODE)
 }
