@@ -1498,6 +1498,94 @@ int phmm_assembly_recover(phmm_handle *h, const void *cfg, uint32_t n_regions, c
                           uint8_t *edge_removed);
 
 /*
+ * phmm_assembly_seqgraph -- the zipped sequence graph, what get_assembly_result does behind the pruned graph (A:1154-1259):
+ * to_sequence_graph (B:54-84), clean_non_ref_paths (B:716-768), the first zip_linear_chains (S:189-369, called at A:1251),
+ * remove_singleton_orphan_vertices (B:392-406) and remove_vertices_not_connected_to_ref_regardless_of_edge_direction
+ * (B:774-793 with B:686-709), for many graphs in ONE call.  It stops at the graph the reference would print as "1.2.pruned",
+ * in front of simplify_graph (A:1284); simplify_graph and the path finder are LEFT OUT.  Integers and bytes: every output
+ * EQUALS a serial restatement of the reference.  A, B as above, S = src/graphs/seq_graph.rs.  Degrees count edges.
+ * Numbering: petgraph's reuse of vacant slots is NOT modelled.  A new vertex or edge takes a fresh index behind all existing
+ * ones; the output is the present elements in ascending model index, renumbered compactly.  So unmerged vertices keep their
+ * relative order and merged vertices follow in the order of their zip starts; untouched edges keep their relative order and
+ * re-created edges follow in creation order.  (The reference's own tests compare sequence graphs by content: graph_equals.)
+ *   (1) conversion   sequence vertex i is the i-th present vertex, sequence edge j the j-th present edge.  A vertex with
+ *                in-degree 0 among the present edges carries all its k bytes, any other its last byte.  An edge keeps is_ref
+ *                and multiplicity
+ *   (2) clean    nothing unless both reference ends exist (the lowest index for which is_ref_source / is_ref_sink holds, with
+ *                "the graph has one node" as written).  The removed in-edges are the least fixed point of: a non-reference
+ *                edge goes if its target is the reference source or the source of a removed edge; the out-edge side is the
+ *                mirror from the reference sink, on the graph the first half left.  Then the orphans go (B:766).  The
+ *                reference pops an edge it has removed, and panics, where a vertex's edge list is pushed a second time and
+ *                still holds a non-reference edge; whether it still does depends on the heap's order.  The contract is the
+ *                order-free superset: a vertex that is pushed twice (it is the swept end, or the far end of a removed edge,
+ *                two times in all) and whose list held a non-reference edge gives the graph PHMM_SEQ_REFERENCE_FAILS and empty
+ *                outputs.  ("The sink is gone after the first half" cannot happen: only non-reference edges go there.)
+ *                Behind PHMM_PRUNE_OP_CONNECT on an acyclic graph this step removes nothing
+ *   (3) zip      a vertex is a start if its out-degree is 1 and its in-degree is not 1, or its one predecessor has out-degree
+ *                above 1; starts are listed in ascending index before anything changes.  A chain runs from its start while
+ *                the last vertex has out-degree 1, the target in-degree 1, the target is not the last vertex and both have
+ *                the same is_reference_node.  A chain of two or more vertices becomes one vertex with the chain's bytes; it
+ *                gets copies of the last vertex's out-edges, newest first, then of the first vertex's in-edges, newest first,
+ *                as that list stands then.  As written: the vertex behind a reference / non-reference break is no start and
+ *                stays unzipped with what follows it; last -> first gives a self-loop; an edge from the end of one chain to
+ *                the start of another is copied twice and survives once, created at the later merge; a ring of interior
+ *                vertices has no start and stays
+ *   (4) orphans  listed before any goes; an isolated vertex stays only if it is the graph's one vertex
+ *   (5) connectivity   kept: the reference source, what reaches it backwards and what it reaches forwards -- NOT weak
+ *                connectivity.  Without a reference source every vertex goes
+ * Inputs: the region arrays, n_k, k and the k-major graph layout as phmm_assembly_recover takes them; vertex_off, edge_off,
+ * edge_src, edge_dst, edge_is_ref, edge_multiplicity of the graphs as they stand (recovery's elements behind each graph's own);
+ *   vertex_seq, vertex_pos   of the raw vertices only: graph g's rows start at vertex_off[g] - new_vertex_off[g]
+ *   new_vertex_off [n_graphs+1], new_vertex_kmer [new vertices x max(k)]   both NULL or both given, as phmm_assembly_recover
+ *                writes them: the last new_vertex_off[g+1] - new_vertex_off[g] vertices of graph g take their k bytes from the rows
+ *   vertex_absent, edge_absent   both NULL or both given, nonzero = not in the graph
+ *   graph_flags [n_graphs] or NULL   phmm_assembly_prune's: a graph with PHMM_PRUNE_HAS_CYCLE or PHMM_PRUNE_NO_REF_ENDS is the
+ *                caller's to drop; it gets PHMM_SEQ_SKIPPED and empty outputs
+ * The regions' bases are staged again (the device needs one byte per vertex and k per source vertex, and the chain hands them
+ * over in no smaller form without host work between the calls).
+ * Outputs.  capacity [3] / required [3] count sequence vertices, sequence edges and sequence bytes, as phmm_assembly_graph's
+ * do: when a capacity is too small the call returns PHMM_ERR_EVENT_CAPACITY with `required` filled and nothing else written;
+ * all capacities 0 is the way to ask (the call does all its work either way, and only the sizes come back).
+ *   per graph    seq_status (PHMM_SEQ_*), n_seq_vertices, n_seq_edges, n_seq_bases, n_chains_zipped (chains merged),
+ *                n_removed_clean (edges step 2 removed), n_removed_unconnected (vertices step 5 removed), seq_ref_source,
+ *                seq_ref_sink (of the final graph, UINT32_MAX if none) [n_graphs]; seq_vertex_off, seq_edge_off, seq_base_off
+ *                [n_graphs+1]
+ *   per sequence vertex   seq_vertex_base_off (inside the graph's bytes; a vertex's bytes end where the next one's start);
+ *                seq_vertex_first: the input vertex that is the chain's first, or the vertex itself; seq_vertex_n_merged
+ *   per sequence edge   seq_edge_src, seq_edge_dst (indices inside the graph), seq_edge_is_ref, seq_edge_multiplicity
+ *   seq_bases [bytes]; vertex_to_seq [vertices] or NULL: the sequence vertex that holds the input vertex's bytes, UINT32_MAX
+ *                where it is gone
+ * One workgroup of 256 lanes works on a graph, in the device workspace whatever the graph's size (no LDS copy of small
+ * graphs); a second kernel sums the sizes and a third writes the output at each graph's offsets, so only the zipped graphs
+ * (and vertex_to_seq, if asked for) cross to the host.  Device workspace kept by the handle: 84 bytes per vertex, 5 per edge
+ * and 16 per sort slot (a graph's edge count rounded up to a power of two).  Limits: a graph's vertices below 2^31 - 1;
+ * vertices x max(k) within 32 bits.  The result is the same from run to run and whatever else is in the batch: the atomics
+ * are integer sums, ORs, minima and maxima, and the one atomic append feeds a sort of distinct keys.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): the cases of phmm_assembly_prune and
+ * phmm_assembly_recover for offsets, endpoints, masks, region offsets, read windows, vertex_seq / vertex_pos and k; one of
+ * new_vertex_off / new_vertex_kmer without the other; capacity or required NULL; a NULL array that has elements; a capacity
+ * above 0 whose arrays are NULL; a graph above the limits.  n_graphs == 0, empty graphs and graphs without edges are fine.
+ * One thread per handle.
+ */
+#define PHMM_SEQ_OK 0u
+#define PHMM_SEQ_SKIPPED 1u
+#define PHMM_SEQ_REFERENCE_FAILS 2u
+int phmm_assembly_seqgraph(phmm_handle *h, uint32_t n_regions, const uint32_t *region_ref_off, const uint8_t *ref_bases,
+                           const uint32_t *region_read_off, const uint32_t *read_off, const uint8_t *read_bases,
+                           const uint32_t *read_first, const uint32_t *read_len, uint32_t n_k, const uint32_t *k,
+                           const uint32_t *vertex_off, const uint32_t *edge_off, const uint32_t *vertex_seq,
+                           const uint32_t *vertex_pos, const uint32_t *edge_src, const uint32_t *edge_dst,
+                           const uint8_t *edge_is_ref, const uint32_t *edge_multiplicity, const uint32_t *new_vertex_off,
+                           const uint8_t *new_vertex_kmer, const uint8_t *vertex_absent, const uint8_t *edge_absent,
+                           const uint32_t *graph_flags, const uint32_t *capacity, uint32_t *required, uint32_t *seq_status,
+                           uint32_t *n_seq_vertices, uint32_t *n_seq_edges, uint32_t *n_seq_bases, uint32_t *n_chains_zipped,
+                           uint32_t *n_removed_clean, uint32_t *n_removed_unconnected, uint32_t *seq_ref_source,
+                           uint32_t *seq_ref_sink, uint32_t *seq_vertex_off, uint32_t *seq_edge_off, uint32_t *seq_base_off,
+                           uint32_t *seq_vertex_base_off, uint32_t *seq_vertex_first, uint32_t *seq_vertex_n_merged,
+                           uint32_t *seq_edge_src, uint32_t *seq_edge_dst, uint8_t *seq_edge_is_ref,
+                           uint32_t *seq_edge_multiplicity, uint8_t *seq_bases, uint32_t *vertex_to_seq);
+
+/*
  * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
  * assembler's haplotypes before a likelihood is computed, for many regions in ONE call: get_variation_events, the trimmer's
  * two spans, every haplotype cut to the padded span, duplicates folded, the rest in the reference's order.  Integers and

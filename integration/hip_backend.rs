@@ -1765,6 +1765,151 @@ pub fn assembly_recover(input: &RecoverInput, cfg: &phmm_recover_config) -> Reco
     }
 }
 
+/// What `assembly_seqgraph` returns: the arrays of `phmm_assembly_seqgraph` as the header lays them out, cut to what was written.
+/// `per_graph`: status, sequence vertices, edges, bytes, chains zipped, edges cleaned, vertices unconnected, reference source, sink.
+pub struct SequenceGraphs {
+    pub per_graph: Vec<[u32; 9]>,
+    pub seq_vertex_off: Vec<u32>,
+    pub seq_edge_off: Vec<u32>,
+    pub seq_base_off: Vec<u32>,
+    pub seq_vertex_base_off: Vec<u32>,
+    pub seq_vertex_first: Vec<u32>,
+    pub seq_vertex_n_merged: Vec<u32>,
+    pub seq_edge_src: Vec<u32>,
+    pub seq_edge_dst: Vec<u32>,
+    pub seq_edge_is_ref: Vec<u8>,
+    pub seq_edge_multiplicity: Vec<u32>,
+    pub seq_bases: Vec<u8>,
+    pub vertex_to_seq: Vec<u32>,
+}
+
+/// The dense arrays `assembly_seqgraph` reads: the regions as `assembly_graph` packed them, the raw vertices' `vertex_seq` /
+/// `vertex_pos`, and the graphs as recovery and `assembly_prune(CONNECT)` left them, k-major (empty slices: no new vertices, no
+/// absent element, no flags).
+pub struct SequenceGraphInput<'a> {
+    pub region_ref_off: &'a [u32],
+    pub ref_bases: &'a [u8],
+    pub region_read_off: &'a [u32],
+    pub read_off: &'a [u32],
+    pub read_bases: &'a [u8],
+    pub k: &'a [u32],
+    pub vertex_off: &'a [u32],
+    pub edge_off: &'a [u32],
+    pub vertex_seq: &'a [u32],
+    pub vertex_pos: &'a [u32],
+    pub edge_src: &'a [u32],
+    pub edge_dst: &'a [u32],
+    pub edge_is_ref: &'a [u8],
+    pub edge_multiplicity: &'a [u32],
+    pub new_vertex_off: &'a [u32],
+    pub new_vertex_kmer: &'a [u8],
+    pub vertex_absent: &'a [u8],
+    pub edge_absent: &'a [u8],
+    pub graph_flags: &'a [u32],
+}
+
+/// The zipped sequence graph of many graphs: `to_sequence_graph`, `clean_non_ref_paths`, the first `zip_linear_chains`, the
+/// orphans and `remove_vertices_not_connected_to_ref_regardless_of_edge_direction`.  Asks for the sizes first (capacities 0), then
+/// calls again with them.  Not compiled here and bound to no call site: the assembler's `get_assembly_result` still builds its
+/// sequence graph on the host.
+pub fn assembly_seqgraph(input: &SequenceGraphInput) -> SequenceGraphs {
+    let n_regions = input.region_ref_off.len().max(1) - 1;
+    let n_graphs = input.k.len() * n_regions;
+    let masks = !input.vertex_absent.is_empty() || !input.edge_absent.is_empty();
+    let or_null = |v: &[u8]| if masks { v.as_ptr() } else { std::ptr::null() };
+    let news = !input.new_vertex_off.is_empty();
+    let mut capacity = [0u32; 3];
+    let mut required = [0u32; 3];
+    loop {
+        let mut per = vec![vec![0u32; n_graphs]; 9];
+        let mut offs = vec![vec![0u32; n_graphs + 1]; 3];
+        let mut vertices = vec![vec![0u32; capacity[0] as usize]; 3];
+        let mut edges = vec![vec![0u32; capacity[1] as usize]; 3];
+        let mut seq_edge_is_ref = vec![0u8; capacity[1] as usize];
+        let mut seq_bases = vec![0u8; capacity[2] as usize];
+        let mut vertex_to_seq = vec![0u32; input.vertex_off.last().copied().unwrap_or(0) as usize];
+        let mut rc = PHMM_OK;
+        with_engine(|h| {
+            rc = unsafe {
+                phmm_assembly_seqgraph(
+                    h,
+                    n_regions as u32,
+                    input.region_ref_off.as_ptr(),
+                    input.ref_bases.as_ptr(),
+                    input.region_read_off.as_ptr(),
+                    input.read_off.as_ptr(),
+                    input.read_bases.as_ptr(),
+                    std::ptr::null(),
+                    std::ptr::null(),
+                    input.k.len() as u32,
+                    input.k.as_ptr(),
+                    input.vertex_off.as_ptr(),
+                    input.edge_off.as_ptr(),
+                    input.vertex_seq.as_ptr(),
+                    input.vertex_pos.as_ptr(),
+                    input.edge_src.as_ptr(),
+                    input.edge_dst.as_ptr(),
+                    input.edge_is_ref.as_ptr(),
+                    input.edge_multiplicity.as_ptr(),
+                    if news { input.new_vertex_off.as_ptr() } else { std::ptr::null() },
+                    if news { input.new_vertex_kmer.as_ptr() } else { std::ptr::null() },
+                    or_null(input.vertex_absent),
+                    or_null(input.edge_absent),
+                    if input.graph_flags.is_empty() { std::ptr::null() } else { input.graph_flags.as_ptr() },
+                    capacity.as_ptr(),
+                    required.as_mut_ptr(),
+                    per[0].as_mut_ptr(),
+                    per[1].as_mut_ptr(),
+                    per[2].as_mut_ptr(),
+                    per[3].as_mut_ptr(),
+                    per[4].as_mut_ptr(),
+                    per[5].as_mut_ptr(),
+                    per[6].as_mut_ptr(),
+                    per[7].as_mut_ptr(),
+                    per[8].as_mut_ptr(),
+                    offs[0].as_mut_ptr(),
+                    offs[1].as_mut_ptr(),
+                    offs[2].as_mut_ptr(),
+                    vertices[0].as_mut_ptr(),
+                    vertices[1].as_mut_ptr(),
+                    vertices[2].as_mut_ptr(),
+                    edges[0].as_mut_ptr(),
+                    edges[1].as_mut_ptr(),
+                    seq_edge_is_ref.as_mut_ptr(),
+                    edges[2].as_mut_ptr(),
+                    seq_bases.as_mut_ptr(),
+                    vertex_to_seq.as_mut_ptr(),
+                )
+            };
+            if rc != PHMM_OK && rc != PHMM_ERR_EVENT_CAPACITY {
+                panic!("HIP assembly_seqgraph failed ({}): {}", rc, last_error(h));
+            }
+        });
+        if rc == PHMM_ERR_EVENT_CAPACITY {
+            capacity = required;
+            continue;
+        }
+        let mut offs = offs.into_iter();
+        let mut vertices = vertices.into_iter();
+        let mut edges = edges.into_iter();
+        return SequenceGraphs {
+            per_graph: (0..n_graphs).map(|g| [per[0][g], per[1][g], per[2][g], per[3][g], per[4][g], per[5][g], per[6][g], per[7][g], per[8][g]]).collect(),
+            seq_vertex_off: offs.next().unwrap(),
+            seq_edge_off: offs.next().unwrap(),
+            seq_base_off: offs.next().unwrap(),
+            seq_vertex_base_off: vertices.next().unwrap(),
+            seq_vertex_first: vertices.next().unwrap(),
+            seq_vertex_n_merged: vertices.next().unwrap(),
+            seq_edge_src: edges.next().unwrap(),
+            seq_edge_dst: edges.next().unwrap(),
+            seq_edge_is_ref,
+            seq_edge_multiplicity: edges.next().unwrap(),
+            seq_bases,
+            vertex_to_seq,
+        };
+    }
+}
+
 /// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
 /// location (closed) and whether it is the reference haplotype.
 pub struct TrimHaplotype<'a> {

@@ -176,6 +176,10 @@ pub const PHMM_RECOVER_END_CANNOT_EXTEND: c_uint = 9;
 pub const PHMM_RECOVER_END_MERGED: c_uint = 10;
 pub const PHMM_RECOVER_END_NO_MERGE_POINT: c_uint = 11;
 pub const PHMM_RECOVER_END_REFERENCE_FAILS: c_uint = 12;
+/// `phmm_assembly_seqgraph`: a graph's status
+pub const PHMM_SEQ_OK: c_uint = 0;
+pub const PHMM_SEQ_SKIPPED: c_uint = 1;
+pub const PHMM_SEQ_REFERENCE_FAILS: c_uint = 2;
 /// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
 /// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
 pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
@@ -1143,6 +1147,59 @@ extern "C" {
         new_edge_pruning_multiplicity: *mut u32,
         new_vertex_kmer: *mut u8,
         edge_removed: *mut u8,
+    ) -> c_int;
+    /// the zipped sequence graph (base_graph.rs:54-84, 716-793, seq_graph.rs:189-369): to_sequence_graph, clean_non_ref_paths, the first
+    /// zip_linear_chains, the orphans and the vertices the reference source neither reaches nor is reached from, for many graphs;
+    /// `new_vertex_off` / `new_vertex_kmer` are null together, as are the two `absent` masks; `graph_flags` and `vertex_to_seq` may be
+    /// null; `capacity` / `required` count sequence vertices, sequence edges and sequence bytes
+    pub fn phmm_assembly_seqgraph(
+        h: *mut phmm_handle,
+        n_regions: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        region_read_off: *const u32,
+        read_off: *const u32,
+        read_bases: *const u8,
+        read_first: *const u32,
+        read_len: *const u32,
+        n_k: u32,
+        k: *const u32,
+        vertex_off: *const u32,
+        edge_off: *const u32,
+        vertex_seq: *const u32,
+        vertex_pos: *const u32,
+        edge_src: *const u32,
+        edge_dst: *const u32,
+        edge_is_ref: *const u8,
+        edge_multiplicity: *const u32,
+        new_vertex_off: *const u32,
+        new_vertex_kmer: *const u8,
+        vertex_absent: *const u8,
+        edge_absent: *const u8,
+        graph_flags: *const u32,
+        capacity: *const u32,
+        required: *mut u32,
+        seq_status: *mut u32,
+        n_seq_vertices: *mut u32,
+        n_seq_edges: *mut u32,
+        n_seq_bases: *mut u32,
+        n_chains_zipped: *mut u32,
+        n_removed_clean: *mut u32,
+        n_removed_unconnected: *mut u32,
+        seq_ref_source: *mut u32,
+        seq_ref_sink: *mut u32,
+        seq_vertex_off: *mut u32,
+        seq_edge_off: *mut u32,
+        seq_base_off: *mut u32,
+        seq_vertex_base_off: *mut u32,
+        seq_vertex_first: *mut u32,
+        seq_vertex_n_merged: *mut u32,
+        seq_edge_src: *mut u32,
+        seq_edge_dst: *mut u32,
+        seq_edge_is_ref: *mut u8,
+        seq_edge_multiplicity: *mut u32,
+        seq_bases: *mut u8,
+        vertex_to_seq: *mut u32,
     ) -> c_int;
     /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
     /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;

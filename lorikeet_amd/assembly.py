@@ -2,7 +2,8 @@
 the verdicts that reject a k before a vertex exists, the sizes of the non-unique set and of the vertex map, and per position
 whether its k-mer is non-unique, threaded, a threading start, the first of its bytes, with its dense id; and the raw
 read-threading graph itself (phmm_assembly_graph): vertices, edges, weights, the reference path, per (k, region); and what the
-assembler prunes from it before it looks for paths (phmm_assembly_prune)."""
+assembler prunes from it before it looks for paths (phmm_assembly_prune), recovers at its dangling ends (phmm_assembly_recover)
+and zips into the sequence graph (phmm_assembly_seqgraph)."""
 import ctypes as C
 
 import numpy as np
@@ -330,3 +331,90 @@ def apply_recovery(graph, pruned, recovered):
     if "k" in graph:
         res["k"] = graph["k"]
     return res
+
+
+SEQ_GRAPH = ("seq_status", "n_seq_vertices", "n_seq_edges", "n_seq_bases", "n_chains_zipped", "n_removed_clean", "n_removed_unconnected",
+             "seq_ref_source", "seq_ref_sink")
+SEQ_OFFSETS = ("seq_vertex_off", "seq_edge_off", "seq_base_off")
+SEQ_VERTEX = ("seq_vertex_base_off", "seq_vertex_first", "seq_vertex_n_merged")
+SEQ_EDGE = (("seq_edge_src", np.uint32), ("seq_edge_dst", np.uint32), ("seq_edge_is_ref", np.uint8), ("seq_edge_multiplicity", np.uint32))
+SEQ_OUTPUTS = SEQ_GRAPH + SEQ_OFFSETS + SEQ_VERTEX + tuple(n for n, _ in SEQ_EDGE) + ("seq_bases", "vertex_to_seq")
+
+
+def sequence_graph(engine, regions, graph, applied=None, connected=None, read_first=None, read_len=None, capacity=None, fill=None, omit=()):
+    """The zipped sequence graph of many graphs (phmm_assembly_seqgraph): to_sequence_graph, clean_non_ref_paths, the first
+    zip_linear_chains, the orphans and the vertices the reference source neither reaches nor is reached from.  regions: what
+    assembly_graph was given (a list of (reference, reads), or pack()'s dict); graph: the dict assembly_graph returns (k,
+    vertex_off, vertex_seq, vertex_pos and, without `applied`, the edge arrays); applied: the dict apply_recovery returns -- its
+    offsets, edges, masks and new vertices replace the graph's -- or None; connected: the dict prune_graph returned for that
+    graph -- its vertex_state / edge_state make the absent masks and its graph_flags travel along -- or a dict with
+    vertex_absent / edge_absent (and graph_flags), or None for applied's masks; read_first / read_len: the windows
+    assembly_graph was given; capacity: (sequence vertices, edges, bytes), None asks the library first (a call with capacities
+    0); fill: a byte the output arrays hold before the call, omit: names of arrays to pass as NULL (tests).  Returns a dict of
+    numpy arrays: seq_status, n_seq_vertices, n_seq_edges, n_seq_bases, n_chains_zipped, n_removed_clean,
+    n_removed_unconnected, seq_ref_source, seq_ref_sink [n_graphs]; seq_vertex_off, seq_edge_off, seq_base_off [n_graphs + 1];
+    the per-vertex, per-edge and seq_bases arrays cut to what was written; vertex_to_seq [vertices]; required.  Raises
+    PhmmError; after PHMM_ERR_EVENT_CAPACITY its `required` attribute holds the sizes."""
+    a = regions if isinstance(regions, dict) else pack(regions)
+    u32 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint32).reshape(-1)  # noqa: E731
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8).reshape(-1)  # noqa: E731
+    region_ref_off, region_read_off, read_off = u32(a.get("region_ref_off")), u32(a.get("region_read_off")), u32(a.get("read_off"))
+    ref_bases, read_bases = u8(a.get("ref_bases")), u8(a.get("read_bases"))
+    read_first, read_len = u32(read_first), u32(read_len)
+    k = u32(graph.get("k"))
+    n_k = 0 if k is None else len(k)
+    n_regions = next((len(x) - 1 for x in (region_ref_off, region_read_off) if x is not None), 0)
+    n_graphs = n_k * n_regions
+    shape = graph if applied is None else applied
+    g32 = {name: u32(shape.get(name)) for name in ("vertex_off", "edge_off", "edge_src", "edge_dst", "edge_multiplicity")}
+    g32.update(vertex_seq=u32(graph.get("vertex_seq")), vertex_pos=u32(graph.get("vertex_pos")))
+    edge_is_ref = u8(shape.get("edge_is_ref"))
+    new_vertex_off, new_vertex_kmer = u32(shape.get("new_vertex_off")), u8(shape.get("new_vertex_kmer"))
+    vertex_absent, edge_absent, graph_flags = u8(shape.get("vertex_absent")), u8(shape.get("edge_absent")), u32(shape.get("graph_flags"))
+    if connected is not None:
+        if "vertex_state" in connected:
+            vertex_absent, edge_absent = u8((np.asarray(connected["vertex_state"]) & _GONE) != 0), u8((np.asarray(connected["edge_state"]) & _GONE) != 0)
+        else:
+            vertex_absent, edge_absent = u8(connected.get("vertex_absent")), u8(connected.get("edge_absent"))
+        graph_flags = u32(connected.get("graph_flags"))
+    n_v = int(g32["vertex_off"][-1]) if n_graphs and g32["vertex_off"] is not None and len(g32["vertex_off"]) else 0
+    new = lambda n, dt: np.zeros(n, dt) if fill is None else np.frombuffer(bytes([fill]) * (n * np.dtype(dt).itemsize), dt).copy()  # noqa: E731
+
+    def call(cap):
+        cap = np.ascontiguousarray(cap, np.uint32)
+        o = dict(required=new(3, np.uint32))
+        o.update({name: new(n_graphs, np.uint32) for name in SEQ_GRAPH})
+        o.update({name: new(n_graphs + 1, np.uint32) for name in SEQ_OFFSETS})
+        o.update({name: new(int(cap[0]), np.uint32) if cap[0] else None for name in SEQ_VERTEX})
+        o.update({name: new(int(cap[1]), dt) if cap[1] else None for name, dt in SEQ_EDGE})
+        o.update(seq_bases=new(int(cap[2]), np.uint8) if cap[2] else None, vertex_to_seq=new(n_v, np.uint32))
+        for name in omit:
+            o[name] = None
+        ptr = lambda name: _p(o[name], _lib.u8p if o[name] is not None and o[name].dtype == np.uint8 else _lib.u32p)  # noqa: E731
+        code = engine.lib.phmm_assembly_seqgraph(
+            engine._h, n_regions, _p(region_ref_off, _lib.u32p), _p(ref_bases, _lib.u8p), _p(region_read_off, _lib.u32p), _p(read_off, _lib.u32p),
+            _p(read_bases, _lib.u8p), _p(read_first, _lib.u32p), _p(read_len, _lib.u32p), n_k, _p(k, _lib.u32p),
+            *[_p(g32[name], _lib.u32p) for name in ("vertex_off", "edge_off", "vertex_seq", "vertex_pos", "edge_src", "edge_dst")],
+            _p(edge_is_ref, _lib.u8p), _p(g32["edge_multiplicity"], _lib.u32p), None if "new_vertex_off" in omit else _p(new_vertex_off, _lib.u32p),
+            None if "new_vertex_kmer" in omit else _p(new_vertex_kmer, _lib.u8p), _p(vertex_absent, _lib.u8p), _p(edge_absent, _lib.u8p),
+            _p(graph_flags, _lib.u32p), None if "capacity" in omit else _p(cap, _lib.u32p), ptr("required"), *[ptr(name) for name in SEQ_OUTPUTS])
+        return code, o
+
+    if capacity is None:
+        code, o = call((0, 0, 0))
+        if code == _lib.PHMM_ERR_EVENT_CAPACITY:
+            code, o = call(o["required"])
+    else:
+        code, o = call(capacity)
+    if code != _lib.PHMM_OK:
+        err = PhmmError(code, engine.last_error())
+        err.required = None if o["required"] is None else o["required"].copy()
+        err.outputs = {name: v for name, v in o.items() if v is not None and name != "required"}
+        raise err
+    n_vertex, n_edge, n_bases = (int(x) for x in o["required"])
+    for name in SEQ_VERTEX:
+        o[name] = np.zeros(0, np.uint32) if o[name] is None else o[name][:n_vertex]
+    for name, dt in SEQ_EDGE:
+        o[name] = np.zeros(0, dt) if o[name] is None else o[name][:n_edge]
+    o["seq_bases"] = np.zeros(0, np.uint8) if o["seq_bases"] is None else o["seq_bases"][:n_bases]
+    return o

@@ -25,6 +25,7 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "graph": ("phmm_graph_internal.hpp", "phmm_graph_kernels.hip", "phmm_asm_internal.hpp", "phmm_asm_kernels.hip"),
     "prune": ("phmm_prune_internal.hpp", "phmm_prune_kernels.hip"),
     "recover": ("phmm_recover_internal.hpp", "phmm_recover_kernels.hip"),
+    "seqgraph": ("phmm_seqgraph_internal.hpp", "phmm_seqgraph_kernels.hip"),
     "trim": ("phmm_trim_internal.hpp", "phmm_trim_kernels.hip", "phmm_events_internal.hpp", "phmm_events_kernels.hip",
              "phmm_cigar_internal.hpp", "phmm_cigar_device.hpp"),
     "regions": ("phmm_regions_internal.hpp", "phmm_regions_kernels.hip"),
