@@ -421,7 +421,10 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
     const int my_ring = sid * (NM + 2);  // first slot of this lane's stream (an index, so the LDS address stays 32-bit math)
     // (LDS byte address of the stream's first slot; q1 = q + 1 is what the loop advances)
     const uint32_t my_rows = (uint32_t)(uintptr_t)(ring + my_ring);  // (the low half of a flat address into LDS is the LDS address)
-    RowConst cA = lds_row(ring, my_ring + (q & NM)), cB;
+    // The address of the row pair in flight.  Before the loop: the pair whose SECOND record is row q (for q & NM == 0 that
+    // is the guard slot behind row NM), so that every step A finds pad1 of its row one record behind `pair_at`.
+    uint32_t pair_at = my_rows + (uint32_t)((q - 1) & NM) * (uint32_t)sizeof(RowConst);
+    RowConst cA = lds_row_at(pair_at, 1), cB;
     int q1 = q + 1;
     const int T = (S_max + CL - 1 + 1) & ~1;  // even number of steps; surplus steps run neutral rows
     // CHAIN_PARK: this lane's column of the parking area, indexed by ring position (the lane is at q now, q + 1 next, ...);
@@ -438,6 +441,9 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
     // have a tick to land (the loads of the issue() in front of the loop, once per wave, are still waited for there).
     // The first tick is shortened by a per-block even phase (the ring only gets further ahead), so that the two
     // waves sharing a SIMD do not run their producers -- the one latency-exposed part -- at the same time.
+    // (the step: cells in groups that share their EXEC writes -- row_update, phmm_device.hpp; K = 22 ... 25 compare packed
+    // haplotype bases and sit at the 256-register limit: they keep the cell-by-cell form)
+    constexpr int STEP = K <= PHMM_SDWA_MIN_K ? ROW_FAST_EXEC_GROUPED : ROW_FAST_EXEC;
     const int phase = (int)((blockIdx.x * 2654435761u) >> 26) & (TPS - 2);
     for (int t0 = 0, t1 = min(T, TPS - phase), tick = 0; t0 < T; t0 = t1, t1 = min(T, t1 + TPS), ++tick) {
         if (tick >= 1) {  // keep the ring one to two ticks (+ phase) ahead of the first lane
@@ -449,7 +455,10 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
             // rows q + 1 and q + 2 lie next to each other (the guard slot repeats row 0 behind the stream's last row)
             // (one full-rate v_mad_u32_u24: the compiler turns the 24-bit multiply back into a 32-bit v_mul_lo_u32, a
             // quarter-rate instruction, plus an add)
-            uint32_t pair_at;
+            // (pad1 of a row is read in the step that injects it, into a register pair that is free by then -- see
+            // lds_pad1_at; the D chain that consumes it comes last in the step, so the read has the whole step to land.
+            // Row q was the second record of the previous pair: no producer tick touches it before the lane has left it.)
+            const double padA = lds_pad1_at(pair_at, 1);
             asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(pair_at) : "v"((uint32_t)(q1 & NM)), "s"((uint32_t)sizeof(RowConst)), "v"(my_rows));
             cB = lds_row_at(pair_at, 0);
             if constexpr (MODE == CHAIN_SUFFIX) {  // the first lane's neighbour is the parked column: M~ and D' of this row from the
@@ -460,13 +469,14 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
                 aM = from_left<CL>(Mp[K - 1], group_head);
                 aI = from_left<CL>(Ip[K - 1], group_head);
             }
-            aD = from_left_inject(Dp[K - 1], cA.pad1, group_head);  // column 0 has D = 0; a RESET row injects the next read's D(0,0)
-            row_update<K, ROW_FAST_EXEC>(Mp, Ip, Dp, bM, bI, bD, aM, aD, cA, hc, 1.0);
+            aD = from_left_inject(Dp[K - 1], padA, group_head);  // column 0 has D = 0; a RESET row injects the next read's D(0,0)
+            row_update<K, STEP>(Mp, Ip, Dp, bM, bI, bD, aM, aD, cA, hc, 1.0);
             if constexpr (MODE == CHAIN_PARK)
                 if (park_lane) park_at[0] = make_double2(Mp[K - 1], Dp[K - 1]);
             // a read's SUM row reaches its emitting lane once per read: a wave-uniform test per step, each on the row
             // that was just consumed (testing cB here as well would wait for its LDS load right after issuing it)
             if (__ballot(cA.x == sum_code) != 0ull) emit(cA);
+            const double padB = lds_pad1_at(pair_at, 0);
             cA = lds_row_at(pair_at, 1);
             if constexpr (MODE == CHAIN_SUFFIX) {
                 bI = from_left_inject(Ip[K - 1], fma(aM, cB.bI, aI * cB.gI), group_head);
@@ -475,8 +485,8 @@ __device__ __forceinline__ void chain_body(const ForwardParams &p, const ChainIt
                 bM = from_left<CL>(Mp[K - 1], group_head);
                 bI = from_left<CL>(Ip[K - 1], group_head);
             }
-            bD = from_left_inject(Dp[K - 1], cB.pad1, group_head);
-            row_update<K, ROW_FAST_EXEC>(Mp, Ip, Dp, aM, aI, aD, bM, bD, cB, hc, 1.0);
+            bD = from_left_inject(Dp[K - 1], padB, group_head);
+            row_update<K, STEP>(Mp, Ip, Dp, aM, aI, aD, bM, bD, cB, hc, 1.0);
             if constexpr (MODE == CHAIN_PARK) {
                 if (park_lane) park_at[1] = make_double2(Mp[K - 1], Dp[K - 1]);
                 park_at += 2;

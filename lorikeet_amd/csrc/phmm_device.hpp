@@ -80,8 +80,8 @@ __device__ __forceinline__ RowConst lds_row(const RowConst *rows, int idx) {
                                                __mul24(idx, (int)sizeof(RowConst)));
 }
 
-// The record at LDS byte address `at` (+ `skip` records): nine 64-bit LDS reads off one address register, the record
-// offset in their immediate fields.
+// The record at LDS byte address `at` (+ `skip` records) without its pad1: eight 64-bit LDS reads off one address
+// register, the record offset in their immediate fields.  pad1 is lds_pad1_at's.
 __device__ __forceinline__ RowConst lds_row_at(uint32_t at, int skip) {
     RowConst r;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -90,7 +90,7 @@ __device__ __forceinline__ RowConst lds_row_at(uint32_t at, int skip) {
     unsigned long long v[sizeof(RowConst) / 8];
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(RowConst) / 8) - 1; ++i) v[i] = w[i];
-    v[8] = w[8];
+    v[8] = 0ull;
     __builtin_memcpy(&r, v, sizeof r);
 #else
     (void)at;
@@ -98,6 +98,22 @@ __device__ __forceinline__ RowConst lds_row_at(uint32_t at, int skip) {
     r = RowConst{};
 #endif
     return r;
+}
+
+// pad1 of that record, by a read of its own (volatile: never paired into a ds_read2_b64 with a neighbour).  The chained
+// sweep injects pad1 through the `old` operand of a DPP move, so pad1's register IS the left neighbour's D' from then on and
+// lives for two steps: as half of a quad that the next record's load writes again, or loaded a step ahead into the
+// register the value of two steps ago still occupies, it had to be copied out (two v_mov_b32 per step).
+__device__ __forceinline__ double lds_pad1_at(uint32_t at, int skip) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const volatile __attribute__((address_space(3))) unsigned long long *LdsU64;
+    const LdsU64 w = (LdsU64)(uintptr_t)at + skip * (int)(sizeof(RowConst) / 8);
+    return __longlong_as_double((long long)w[8]);
+#else
+    (void)at;
+    (void)skip;
+    return 0.0;
+#endif
 }
 
 struct LdsView {
@@ -134,7 +150,9 @@ struct HapCols {
 // no EXEC round trip, which is faster when a wave has a SIMD to itself (small launches; compiled for small K only).
 // Otherwise the general form: `imx` multiplies the indel->match term (1.0 for pre-scaled rows) and the
 // compare honours the haplotype wildcard mask.
-enum : int { ROW_GENERAL = 0, ROW_FAST_CND = 1, ROW_FAST_EXEC = 2, ROW_FAST_EXEC_PRED = 3 };
+// FAST_EXEC_GROUPED: FAST_EXEC's operations with the masked multiplies of three cells issued together, so that three
+// cells write EXEC four times instead of six (the chained f64 sweep; K <= PHMM_SDWA_MIN_K).
+enum : int { ROW_GENERAL = 0, ROW_FAST_CND = 1, ROW_FAST_EXEC = 2, ROW_FAST_EXEC_PRED = 3, ROW_FAST_EXEC_GROUPED = 4 };
 
 template <int K, int MODE>
 __device__ __forceinline__ void row_update(double (&Mp)[K], double (&Ip)[K], double (&Dp)[K], const double plM,
@@ -142,6 +160,89 @@ __device__ __forceinline__ void row_update(double (&Mp)[K], double (&Ip)[K], dou
                                            const RowConst &c, const HapCols<K> &hc, const double imx,
                                            const uint64_t live = ~0ull) {
     const uint16_t x16 = (uint16_t)c.x;
+    if constexpr (MODE == ROW_FAST_EXEC_GROUPED) {
+        // FAST_EXEC's cell (below), operation for operation, so every result keeps its bits -- but the cells of columns
+        // K-1 ... 1 go three at a time (a pair or a single cell where fewer are left) in ONE asm statement:
+        //   for each cell of the group, right to left:  its mask (the first cell's was made behind the group before),
+        //       M~(k) = D'(k-1)*dDp + I^(k-1);  M~(k) += M~(k-1)*mm;  and, but for the last cell, I^(k-1) = I^(k-1)*gI + M~(k-1)*bI
+        //   { EXEC = mask_k;  M~(k) *= px }  for each cell, oldest first;  EXEC = -1
+        //   the first mask of the next group;  I^ of the last cell's column
+        // A write of EXEC is not free: FAST_EXEC's two per cell (38 in a step of K = 19) cost the chained sweep more than
+        // its step's eleven instructions around the cells do -- three cells on four writes run 2 % faster, two cells on
+        // three 1.5 %, while taking three vector instructions out of the step gained nothing (NOTEBOOK.md, "The chained
+        // f64 sweep's EXEC writes").  The order matters as much as the count (the same operations with the multiply two
+        // instructions behind its FMA: 19 % slower; groups written as one statement per phase: half the gain), so a group
+        // is one statement and keeps FAST_EXEC's order wherever it can.  A group's masks live in SGPR pairs meanwhile.
+        static_assert(K <= PHMM_SDWA_MIN_K, "grouped cells compare unpacked haplotype bases");
+#define PHMM_G_C(m, y) "v_cmp_ne_u32_e64 %[" m "], %[x], %[" y "]\n\t"
+#define PHMM_G_M(M, D, I, Ml) "v_fma_f64 %[" M "], %[" D "], %[dDp], %[" I "]\n\tv_fma_f64 %[" M "], %[" Ml "], %[mm], %[" M "]\n\t"
+#define PHMM_G_I(I, Ml) "v_mul_f64 %[" I "], %[" I "], %[gI]\n\tv_fma_f64 %[" I "], %[" Ml "], %[bI], %[" I "]\n\t"
+#define PHMM_G_X(m, M) "s_mov_b64 exec, %[" m "]\n\tv_mul_f64 %[" M "], %[px], %[" M "]\n\t"
+#define PHMM_G_ALL "s_mov_b64 exec, -1\n\t"
+#define PHMM_G_CONST [dDp] "v"(c.dDp), [mm] "v"(c.mm), [x] "v"(c.x), [px] "v"(c.px), [gI] "v"(c.gI), [bI] "v"(c.bI), [mk] "s"(mask)
+        uint64_t mask;  // mismatch mask of the first cell of the group about to be updated
+        asm volatile("v_cmp_ne_u32_e64 %0, %1, %2" : "=s"(mask) : "v"(c.x), "v"((uint32_t)hc.base(K - 1)));
+        asm volatile(PHMM_G_I("I", "M") : [I] "+v"(Ip[K - 1]) : [M] "v"(Mp[K - 1]), [gI] "v"(c.gI), [bI] "v"(c.bI));
+        static_for_down<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            constexpr int n = (K - 1 - k) % 3 != 0 ? 0 : k >= 3 ? 3 : k;  // cells of the group that starts at column k
+            // (columns left of the group's cells: clamped where the group is shorter, and then not named)
+            constexpr int k1 = k > 1 ? k - 1 : 0, k2 = k > 2 ? k - 2 : 0, k3 = k > 3 ? k - 3 : 0;
+            uint64_t next = 0, mb, mc;
+            (void)next, (void)mb, (void)mc, (void)k1, (void)k2, (void)k3;
+            if constexpr (n == 3) {
+                const uint32_t yb = (uint32_t)hc.base(k1), yc = (uint32_t)hc.base(k2), yd = (uint32_t)hc.base(k3);
+                asm volatile(PHMM_G_C("mb", "yb") PHMM_G_M("Ma", "Db", "Ib", "Mb") PHMM_G_I("Ib", "Mb")
+                             PHMM_G_C("mc", "yc") PHMM_G_M("Mb", "Dc", "Ic", "Mc") PHMM_G_I("Ic", "Mc")
+                             PHMM_G_M("Mc", "Dd", "Id", "Md")
+                             PHMM_G_X("mk", "Ma") PHMM_G_X("mb", "Mb") PHMM_G_X("mc", "Mc") PHMM_G_ALL
+                             PHMM_G_C("mn", "yd") PHMM_G_I("Id", "Md")
+                             : [Ma] "=&v"(Mp[k]), [Mb] "+v"(Mp[k1]), [Mc] "+v"(Mp[k2]), [Ib] "+v"(Ip[k1]), [Ic] "+v"(Ip[k2]),
+                               [Id] "+v"(Ip[k3]), [mn] "=&s"(next), [mb] "=&s"(mb), [mc] "=&s"(mc)
+                             : [Db] "v"(Dp[k1]), [Dc] "v"(Dp[k2]), [Dd] "v"(Dp[k3]), [Md] "v"(Mp[k3]), [yb] "v"(yb), [yc] "v"(yc),
+                               [yd] "v"(yd), PHMM_G_CONST);
+                mask = next;
+            } else if constexpr (n == 2) {
+                const uint32_t yb = (uint32_t)hc.base(k1), yc = (uint32_t)hc.base(k2);
+                asm volatile(PHMM_G_C("mb", "yb") PHMM_G_M("Ma", "Db", "Ib", "Mb") PHMM_G_I("Ib", "Mb")
+                             PHMM_G_M("Mb", "Dc", "Ic", "Mc")
+                             PHMM_G_X("mk", "Ma") PHMM_G_X("mb", "Mb") PHMM_G_ALL
+                             PHMM_G_C("mn", "yc") PHMM_G_I("Ic", "Mc")
+                             : [Ma] "=&v"(Mp[k]), [Mb] "+v"(Mp[k1]), [Ib] "+v"(Ip[k1]), [Ic] "+v"(Ip[k2]), [mn] "=&s"(next),
+                               [mb] "=&s"(mb)
+                             : [Db] "v"(Dp[k1]), [Dc] "v"(Dp[k2]), [Mc] "v"(Mp[k2]), [yb] "v"(yb), [yc] "v"(yc), PHMM_G_CONST);
+                mask = next;
+            } else if constexpr (n == 1) {
+                const uint32_t yb = (uint32_t)hc.base(k1);
+                asm volatile(PHMM_G_M("Ma", "Db", "Ib", "Mb") PHMM_G_X("mk", "Ma") PHMM_G_ALL
+                             PHMM_G_C("mn", "yb") PHMM_G_I("Ib", "Mb")
+                             : [Ma] "=&v"(Mp[k]), [Ib] "+v"(Ip[k1]), [mn] "=&s"(next)
+                             : [Db] "v"(Dp[k1]), [Mb] "v"(Mp[k1]), [yb] "v"(yb), PHMM_G_CONST);
+                mask = next;
+            } else if constexpr (k == 0) {
+                // no column to the left in this lane: the neighbour's values come in (plM, plI, plD).  The two FMAs depend
+                // on nothing this step computes, so the compiler may place them anywhere before the masked multiply.
+                double m;
+                asm(PHMM_G_M("M", "Dl", "Il", "Ml") : [M] "=&v"(m) : [Dl] "v"(plD), [dDp] "v"(c.dDp), [Il] "v"(plI), [Ml] "v"(plM), [mm] "v"(c.mm));
+                asm volatile(PHMM_G_X("mk", "M") PHMM_G_ALL : [M] "+v"(m) : [px] "v"(c.px), [mk] "s"(mask));
+                Mp[0] = m;
+            }
+        });
+#undef PHMM_G_C
+#undef PHMM_G_M
+#undef PHMM_G_I
+#undef PHMM_G_X
+#undef PHMM_G_ALL
+#undef PHMM_G_CONST
+        double leftM = lM, leftD = lD;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            Dp[k] = fma(leftD, c.dd, leftM);
+            leftM = Mp[k];
+            leftD = Dp[k];
+        }
+        return;
+    }
     if constexpr (MODE == ROW_FAST_EXEC || MODE == ROW_FAST_EXEC_PRED) {
         // Pre-scaled rows (pm == 1).  One cell = one asm statement in a fixed order:
         //   M~(k)  = D'(k-1)*dDp + I^(k-1);  M~(k) += M~(k-1)*mm          (row i-1 values of column k-1)
