@@ -1586,6 +1586,98 @@ int phmm_assembly_seqgraph(phmm_handle *h, uint32_t n_regions, const uint32_t *r
                            uint32_t *seq_edge_multiplicity, uint8_t *seq_bases, uint32_t *vertex_to_seq);
 
 /*
+ * phmm_assembly_best_paths -- the k best haplotype paths of many sequence graphs in ONE call: what find_best_path
+ * (A:709-899) asks of GraphBasedKBestHaplotypeFinder, and Path::get_bases behind it.  F = src/graphs/k_best_haplotype_finder.rs,
+ * G = src/graphs/graph_based_k_best_haplotype_finder.rs, K = src/graphs/k_best_haplotype.rs, P = src/graphs/path.rs.  Taken as
+ * written, not repaired; every output EQUALS a serial restatement of the reference, scores to the bit.  simplify_graph, the
+ * one-vertex "dummy" fix-up (A:1319-1331) and the CIGAR filters (A:795-858) are LEFT OUT.
+ * The graph is taken as created: an edge's index inside its graph is its petgraph EdgeIndex, a vertex's out-edges iterate
+ * newest first (descending index).  A vertex may have 0 bytes.
+ *   (1) cycles   F:71-182, only if the WHOLE graph is cyclic (parts the source cannot reach included).  From every source a
+ *                depth-first walk over out-edges, newest first, with a fresh visited set per source; the set is never
+ *                shrunk on return, so an edge to ANY visited vertex goes -- cross and forward edges too.  A sink returns
+ *                true at once: it is never marked and never explored, so edges into a sink stay and its out-edges are not
+ *                walked.  Every child is visited.  A visited vertex that reaches no sink through first visits goes with
+ *                its edges; unvisited vertices stay.  No path found: PHMM_PATHS_NO_PATH (first assert; also a cyclic graph
+ *                with no source); nothing to remove: PHMM_PATHS_CYCLES_STAY (second assert: the cycle is out of reach).
+ *                Both give empty outputs and zero marks
+ *   (2) search   G:64-132.  The queue starts with a zero-edge path per source.  Pop the greatest.  At a sink it is a result
+ *                and is not extended.  Elsewhere count[v] += 1 and, if count[v] < max_paths, one child per present out-edge
+ *                is pushed.  Stops when the queue is empty or max_paths results exist
+ *   (3) score    child = parent + (log10(m) - log10(T)), T the sum of the vertex's present out-edge multiplicities in 64
+ *                bits: three roundings, no contraction.  Order (K:103-112): OrderedFloat's -- NaN greatest and equal to
+ *                itself, -0.0 equal to 0.0 -- then the lexicographically smaller edge list wins, a proper prefix before its
+ *                extension; zero-edge paths of several sources, which tie completely, go in ascending vertex index.  m == 0
+ *                with T > 0 gives -inf; m == 0 with T == 0 gives NaN (the dummy edge's path, which pops first); a NaN is
+ *                written as 0x7ff8000000000000 whatever sign the subtraction gave it.  is_ref: the AND of the edges'
+ *                is_ref, true for a zero-edge path
+ *   (4) log10    the handle keeps L[n] = log10((double)n) on the device, built on the host by the C library's log10, one
+ *                call per entry, L[0] = -inf, grown on demand to the largest per-vertex total (over the out-edges as given)
+ *                of a call, up to PHMM_PATHS_MAX_WEIGHT.  A graph with a larger total gets PHMM_PATHS_WEIGHT_RANGE
+ *   (5) bases    P:234-267: the first vertex's bytes, then each edge target's
+ *   (6) budget   a graph whose search would create more than max_nodes_per_graph tree nodes (the sources' included) gets
+ *                PHMM_PATHS_BUDGET and no paths; the marks and counts of step 1 stay.  The pool of a graph is
+ *                min(budget, sources + (max_paths - 1) x edges), which no search can exceed
+ *   (7) duplicates   A:770 with Haplotype::eq on bytes, only with the region arrays: for region r the paths of graphs
+ *                k x n_regions + r in k order and rank order are what find_best_path meets.  path_first_equal[p]:
+ *                UINT32_MAX = first of its bytes; PHMM_PATHS_EQUALS_REF = the region's reference bytes (the result set
+ *                starts with the reference haplotype); else the call-wide index of the earliest path with these bytes
+ * Inputs: n_graphs; seq_vertex_off, seq_edge_off, seq_base_off [n_graphs+1], seq_vertex_base_off, seq_edge_src, seq_edge_dst,
+ * seq_edge_is_ref, seq_edge_multiplicity, seq_bases as phmm_assembly_seqgraph writes them;
+ *   seq_status [n_graphs] or NULL   a graph whose status is not PHMM_SEQ_OK gets PHMM_PATHS_SKIPPED
+ *   graph_source, graph_sink [n_graphs]   seq_ref_source / seq_ref_sink; UINT32_MAX in either gives PHMM_PATHS_NO_ENDS (A:739-742)
+ *   vertex_role [vertices] or NULL   bit 0 a source, bit 1 a sink; when given it replaces the two arrays (they may be NULL).
+ *                An empty source or sink set gives an acyclic graph 0 paths
+ *   max_paths    num_best_haplotypes_per_graph; UINT32_MAX = usize::MAX.  max_nodes_per_graph: nonzero
+ *   n_regions, n_k, region_ref_off [n_regions+1], ref_bases   all given (n_graphs == n_k x n_regions, k-major) or 0 / NULL
+ * Outputs.  capacity [3] / required [3] count paths, path edges and haplotype bytes, as phmm_assembly_seqgraph's do:
+ * PHMM_ERR_EVENT_CAPACITY with `required` filled and nothing else written; all capacities 0 asks for the sizes.
+ *   per graph    paths_status (PHMM_PATHS_*), n_paths, n_popped (queue pops), n_cycle_edges_removed (edges gone behind step 1,
+ *                those of removed vertices included), n_cycle_vertices_removed [n_graphs]; path_off, path_edge_off,
+ *                hap_base_off [n_graphs+1]
+ *   per path, call-wide, a graph's paths in pop order   path_score, path_is_ref, path_n_edges [paths]; hap_off [capacity[0]+1]:
+ *                path p's bytes are hap_bases[hap_off[p] .. hap_off[p+1]) -- the alt_off / alt_bases of phmm_calculate_cigar;
+ *                path_first_equal [paths] or NULL
+ *   path_edges [path edges]   indices inside the graph, a path's edges in order, the paths one behind the other
+ *   hap_bases [bytes]; edge_removed [edges], vertex_removed [vertices] or NULL: nonzero = gone in step 1 (an edge: bit 0 the
+ *                walk removed it, bit 1 it went with a vertex)
+ * One wave works on a graph, in the handle's device workspace (20 bytes per vertex, 4 per edge, 45 per node of the pools);
+ * the queue is an unsorted array and a pop is a wave argmax under the reference's order, ties by walking the two paths to
+ * their common ancestor in the search tree.  Then an offsets kernel, an output kernel (a wave per path) and the duplicate
+ * kernel (a wave per path).  One writer per element; the bytes of a call are the same from run to run and whatever else is
+ * in the batch.
+ * PHMM_ERR_INVALID_ARG (nothing written; phmm_last_error names the first offender): offsets not starting at 0 or
+ * descending; an endpoint outside its graph; a seq_vertex_base_off past the graph's bytes or descending; a source or sink
+ * that is neither a vertex nor UINT32_MAX; a role above 3; max_paths or max_nodes_per_graph 0; the region arguments given
+ * in part, or n_k x n_regions != n_graphs; path_first_equal without them; capacity or required NULL; a NULL array that has
+ * elements; a capacity above 0 whose arrays are NULL; node pools beyond 32 bits in sum; paths, path edges or haplotype
+ * bytes that reach 2^32 - 1 in sum (known only behind the search: no capacity could hold them, so it is not
+ * PHMM_ERR_EVENT_CAPACITY).  n_graphs == 0, empty graphs and
+ * graphs without edges are fine.  One thread per handle.
+ */
+#define PHMM_PATHS_OK 0u
+#define PHMM_PATHS_SKIPPED 1u
+#define PHMM_PATHS_NO_ENDS 2u
+#define PHMM_PATHS_NO_PATH 3u
+#define PHMM_PATHS_CYCLES_STAY 4u
+#define PHMM_PATHS_WEIGHT_RANGE 5u
+#define PHMM_PATHS_BUDGET 6u
+#define PHMM_PATHS_MAX_WEIGHT 1048576u
+#define PHMM_PATHS_EQUALS_REF 4294967294u
+int phmm_assembly_best_paths(phmm_handle *h, uint32_t n_graphs, const uint32_t *seq_vertex_off, const uint32_t *seq_edge_off,
+                             const uint32_t *seq_base_off, const uint32_t *seq_vertex_base_off, const uint32_t *seq_edge_src,
+                             const uint32_t *seq_edge_dst, const uint8_t *seq_edge_is_ref, const uint32_t *seq_edge_multiplicity,
+                             const uint8_t *seq_bases, const uint32_t *seq_status, const uint32_t *graph_source,
+                             const uint32_t *graph_sink, const uint8_t *vertex_role, uint32_t max_paths,
+                             uint32_t max_nodes_per_graph, uint32_t n_regions, uint32_t n_k, const uint32_t *region_ref_off,
+                             const uint8_t *ref_bases, const uint32_t *capacity, uint32_t *required, uint32_t *paths_status,
+                             uint32_t *n_paths, uint32_t *n_popped, uint32_t *n_cycle_edges_removed,
+                             uint32_t *n_cycle_vertices_removed, uint32_t *path_off, uint32_t *path_edge_off,
+                             uint32_t *hap_base_off, double *path_score, uint8_t *path_is_ref, uint32_t *path_n_edges,
+                             uint32_t *hap_off, uint32_t *path_first_equal, uint32_t *path_edges, uint8_t *hap_bases,
+                             uint8_t *edge_removed, uint8_t *vertex_removed);
+
+/*
  * phmm_trim_regions -- what the reference's call_region (src/haplotype/haplotype_caller_engine.rs:1194-1243) does with the
  * assembler's haplotypes before a likelihood is computed, for many regions in ONE call: get_variation_events, the trimmer's
  * two spans, every haplotype cut to the padded span, duplicates folded, the rest in the reference's order.  Integers and

@@ -1910,6 +1910,133 @@ pub fn assembly_seqgraph(input: &SequenceGraphInput) -> SequenceGraphs {
     }
 }
 
+/// What `assembly_best_paths` returns: the arrays of `phmm_assembly_best_paths` as the header lays them out, cut to what was
+/// written.  `per_graph`: status (`PHMM_PATHS_*`), paths, queue pops, edges and vertices the cycle removal took.  `hap_off` /
+/// `hap_bases` are the `alt_off` / `alt_bases` of `calculate_cigar`.
+pub struct BestPaths {
+    pub per_graph: Vec<[u32; 5]>,
+    pub path_off: Vec<u32>,
+    pub path_edge_off: Vec<u32>,
+    pub hap_base_off: Vec<u32>,
+    pub path_score: Vec<f64>,
+    pub path_is_ref: Vec<u8>,
+    pub path_n_edges: Vec<u32>,
+    pub hap_off: Vec<u32>,
+    pub path_first_equal: Vec<u32>,
+    pub path_edges: Vec<u32>,
+    pub hap_bases: Vec<u8>,
+}
+
+/// The k best haplotype paths of the graphs `assembly_seqgraph` returned, k-major: `GraphBasedKBestHaplotypeFinder` from each
+/// graph's reference source to its reference sink, `Path::get_bases`, and which paths `find_best_path` would find in its result
+/// set already (`regions`: `n_k` graphs per region, `region_ref_off` and `ref_bases` of the regions' reference haplotypes; `None`
+/// asks for no duplicate marks and leaves `path_first_equal` empty).  Asks for the sizes first (capacities 0), then calls again
+/// with them: two passes at the most.  Not compiled here and bound to no call site: `find_best_path` still searches on the host.
+pub fn assembly_best_paths(
+    graphs: &SequenceGraphs,
+    regions: Option<(usize, &[u32], &[u8])>,
+    max_paths: u32,
+    max_nodes_per_graph: u32,
+) -> BestPaths {
+    let n_graphs = graphs.per_graph.len();
+    let (n_k, n_regions) = match regions {
+        Some((n_k, region_ref_off, _)) => (n_k, region_ref_off.len().max(1) - 1),
+        None => (0, 0),
+    };
+    let (region_ref_off, ref_bases) = match regions {
+        Some((_, region_ref_off, ref_bases)) => (region_ref_off.as_ptr(), ref_bases.as_ptr()),
+        None => (std::ptr::null(), std::ptr::null()),
+    };
+    let status: Vec<u32> = graphs.per_graph.iter().map(|g| g[0]).collect();
+    let source: Vec<u32> = graphs.per_graph.iter().map(|g| g[7]).collect();
+    let sink: Vec<u32> = graphs.per_graph.iter().map(|g| g[8]).collect();
+    let mut capacity = [0u32; 3];
+    let mut required = [0u32; 3];
+    for pass in 0..2 {
+        let mut per = vec![vec![0u32; n_graphs]; 5];
+        let mut offs = vec![vec![0u32; n_graphs + 1]; 3];
+        let mut path_score = vec![0f64; capacity[0] as usize];
+        let mut path_is_ref = vec![0u8; capacity[0] as usize];
+        let mut path_n_edges = vec![0u32; capacity[0] as usize];
+        let mut hap_off = vec![0u32; capacity[0] as usize + 1];
+        let mut path_first_equal = vec![0u32; if regions.is_some() { capacity[0] as usize } else { 0 }];
+        let mut path_edges = vec![0u32; capacity[1] as usize];
+        let mut hap_bases = vec![0u8; capacity[2] as usize];
+        let mut rc = PHMM_OK;
+        with_engine(|h| {
+            rc = unsafe {
+                phmm_assembly_best_paths(
+                    h,
+                    n_graphs as u32,
+                    graphs.seq_vertex_off.as_ptr(),
+                    graphs.seq_edge_off.as_ptr(),
+                    graphs.seq_base_off.as_ptr(),
+                    graphs.seq_vertex_base_off.as_ptr(),
+                    graphs.seq_edge_src.as_ptr(),
+                    graphs.seq_edge_dst.as_ptr(),
+                    graphs.seq_edge_is_ref.as_ptr(),
+                    graphs.seq_edge_multiplicity.as_ptr(),
+                    graphs.seq_bases.as_ptr(),
+                    status.as_ptr(),
+                    source.as_ptr(),
+                    sink.as_ptr(),
+                    std::ptr::null(),
+                    max_paths,
+                    max_nodes_per_graph,
+                    n_regions as u32,
+                    n_k as u32,
+                    region_ref_off,
+                    ref_bases,
+                    capacity.as_ptr(),
+                    required.as_mut_ptr(),
+                    per[0].as_mut_ptr(),
+                    per[1].as_mut_ptr(),
+                    per[2].as_mut_ptr(),
+                    per[3].as_mut_ptr(),
+                    per[4].as_mut_ptr(),
+                    offs[0].as_mut_ptr(),
+                    offs[1].as_mut_ptr(),
+                    offs[2].as_mut_ptr(),
+                    path_score.as_mut_ptr(),
+                    path_is_ref.as_mut_ptr(),
+                    path_n_edges.as_mut_ptr(),
+                    hap_off.as_mut_ptr(),
+                    if regions.is_some() { path_first_equal.as_mut_ptr() } else { std::ptr::null_mut() },
+                    path_edges.as_mut_ptr(),
+                    hap_bases.as_mut_ptr(),
+                    std::ptr::null_mut(),
+                    std::ptr::null_mut(),
+                )
+            };
+            if rc != PHMM_OK && rc != PHMM_ERR_EVENT_CAPACITY {
+                panic!("HIP assembly_best_paths failed ({}): {}", rc, last_error(h));
+            }
+        });
+        if rc == PHMM_ERR_EVENT_CAPACITY {
+            if pass == 1 {
+                panic!("HIP assembly_best_paths: the sizes {:?} it asked for did not suffice", capacity);
+            }
+            capacity = required;
+            continue;
+        }
+        let mut offs = offs.into_iter();
+        return BestPaths {
+            per_graph: (0..n_graphs).map(|g| [per[0][g], per[1][g], per[2][g], per[3][g], per[4][g]]).collect(),
+            path_off: offs.next().unwrap(),
+            path_edge_off: offs.next().unwrap(),
+            hap_base_off: offs.next().unwrap(),
+            path_score,
+            path_is_ref,
+            path_n_edges,
+            hap_off,
+            path_first_equal,
+            path_edges,
+            hap_bases,
+        };
+    }
+    unreachable!("the second pass returns or panics")
+}
+
 /// One haplotype of the assembler's result set for `trim_regions`: its bases, CIGAR, `alignment_start_hap_wrt_ref`, genome
 /// location (closed) and whether it is the reference haplotype.
 pub struct TrimHaplotype<'a> {

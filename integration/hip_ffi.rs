@@ -180,6 +180,17 @@ pub const PHMM_RECOVER_END_REFERENCE_FAILS: c_uint = 12;
 pub const PHMM_SEQ_OK: c_uint = 0;
 pub const PHMM_SEQ_SKIPPED: c_uint = 1;
 pub const PHMM_SEQ_REFERENCE_FAILS: c_uint = 2;
+/// `phmm_assembly_best_paths`: a graph's status, the largest per-vertex total of multiplicities the log10 table serves, and the
+/// `path_first_equal` of a path whose bytes are the region's reference (`u32::MAX`: the first of its bytes)
+pub const PHMM_PATHS_OK: c_uint = 0;
+pub const PHMM_PATHS_SKIPPED: c_uint = 1;
+pub const PHMM_PATHS_NO_ENDS: c_uint = 2;
+pub const PHMM_PATHS_NO_PATH: c_uint = 3;
+pub const PHMM_PATHS_CYCLES_STAY: c_uint = 4;
+pub const PHMM_PATHS_WEIGHT_RANGE: c_uint = 5;
+pub const PHMM_PATHS_BUDGET: c_uint = 6;
+pub const PHMM_PATHS_MAX_WEIGHT: c_uint = 1048576;
+pub const PHMM_PATHS_EQUALS_REF: c_uint = 4294967294;
 /// `phmm_trim_regions`: the two bits of `variation_present`, what became of an input haplotype (a rank otherwise), the statuses of
 /// a region whose trimming panics in the reference (beside `PHMM_EV_STATUS_*` for a failed event map)
 pub const PHMM_TRIM_VARIATION_SPAN: c_uint = 1;
@@ -1200,6 +1211,52 @@ extern "C" {
         seq_edge_multiplicity: *mut u32,
         seq_bases: *mut u8,
         vertex_to_seq: *mut u32,
+    ) -> c_int;
+    /// the k best haplotype paths of many sequence graphs (k_best_haplotype_finder.rs:71-182, graph_based_k_best_haplotype_finder.rs:64-132,
+    /// k_best_haplotype.rs:86-112, path.rs:234-267): the cycle removal as written, the best-first search, the paths' bases and the
+    /// duplicate marks; `seq_status`, `vertex_role` (then `graph_source` / `graph_sink` too), the region arguments, `path_first_equal`,
+    /// `edge_removed` and `vertex_removed` may be null / 0; `capacity` / `required` count paths, path edges and haplotype bytes
+    pub fn phmm_assembly_best_paths(
+        h: *mut phmm_handle,
+        n_graphs: u32,
+        seq_vertex_off: *const u32,
+        seq_edge_off: *const u32,
+        seq_base_off: *const u32,
+        seq_vertex_base_off: *const u32,
+        seq_edge_src: *const u32,
+        seq_edge_dst: *const u32,
+        seq_edge_is_ref: *const u8,
+        seq_edge_multiplicity: *const u32,
+        seq_bases: *const u8,
+        seq_status: *const u32,
+        graph_source: *const u32,
+        graph_sink: *const u32,
+        vertex_role: *const u8,
+        max_paths: u32,
+        max_nodes_per_graph: u32,
+        n_regions: u32,
+        n_k: u32,
+        region_ref_off: *const u32,
+        ref_bases: *const u8,
+        capacity: *const u32,
+        required: *mut u32,
+        paths_status: *mut u32,
+        n_paths: *mut u32,
+        n_popped: *mut u32,
+        n_cycle_edges_removed: *mut u32,
+        n_cycle_vertices_removed: *mut u32,
+        path_off: *mut u32,
+        path_edge_off: *mut u32,
+        hap_base_off: *mut u32,
+        path_score: *mut f64,
+        path_is_ref: *mut u8,
+        path_n_edges: *mut u32,
+        hap_off: *mut u32,
+        path_first_equal: *mut u32,
+        path_edges: *mut u32,
+        hap_bases: *mut u8,
+        edge_removed: *mut u8,
+        vertex_removed: *mut u8,
     ) -> c_int;
     /// what call_region does with the assembler's haplotypes before a likelihood is computed (haplotype_caller_engine.rs:1194-1243):
     /// the trimmer's spans, every haplotype cut to the padded span, duplicates folded, the rest in the BTreeMap's order, dense;

@@ -8,7 +8,7 @@ creating an engine does (there is no CPU fallback).
 from .activity import activity_profile  # noqa: F401
 from .finalize import finalize_reads  # noqa: F401
 from .phase import phase_calls  # noqa: F401
-from .assembly import apply_recovery, assembly_graph, assembly_kmers, prune_graph, recover_dangling_ends, sequence_graph  # noqa: F401
+from .assembly import apply_recovery, assembly_graph, assembly_kmers, best_paths, prune_graph, recover_dangling_ends, sequence_graph  # noqa: F401
 from .trim import trim_regions  # noqa: F401
 from .assembly_regions import assembly_regions  # noqa: F401
 from .batch import Read, RegionBatch  # noqa: F401

@@ -56,6 +56,9 @@ PHMM_RECOVER_OP_TAILS, PHMM_RECOVER_OP_HEADS, PHMM_RECOVER_KIND_TAIL, PHMM_RECOV
  PHMM_RECOVER_END_TOO_FEW_MATCHING, PHMM_RECOVER_END_WHOLE_INSERTION, PHMM_RECOVER_END_TOO_MANY_MISMATCHES, PHMM_RECOVER_END_CANNOT_PUSH_REF,
  PHMM_RECOVER_END_CANNOT_EXTEND, PHMM_RECOVER_END_MERGED, PHMM_RECOVER_END_NO_MERGE_POINT, PHMM_RECOVER_END_REFERENCE_FAILS) = range(13)
 PHMM_SEQ_OK, PHMM_SEQ_SKIPPED, PHMM_SEQ_REFERENCE_FAILS = 0, 1, 2
+(PHMM_PATHS_OK, PHMM_PATHS_SKIPPED, PHMM_PATHS_NO_ENDS, PHMM_PATHS_NO_PATH, PHMM_PATHS_CYCLES_STAY, PHMM_PATHS_WEIGHT_RANGE,
+ PHMM_PATHS_BUDGET) = range(7)
+PHMM_PATHS_MAX_WEIGHT, PHMM_PATHS_EQUALS_REF = 1 << 20, 0xfffffffe
 PHMM_REG_ACTIVE, PHMM_REG_FORCED, PHMM_REG_OVER_DEPTH = 1, 2, 4
 PHMM_REG_STATUS_MIN_REGION_SIZE, PHMM_REG_STATUS_START_PAST_CONTIG = -1, -2
 PHMM_EV_STATUS_BAD_OPERATOR, PHMM_EV_STATUS_BLOCK, PHMM_EV_STATUS_MERGE, PHMM_EV_STATUS_CIGAR_OVERRUN, PHMM_EV_STATUS_ALLELES = -1, -2, -3, -4, -5
@@ -205,6 +208,9 @@ SYMBOLS = [
                                         u32p, u32p, u32p, u8p, u32p, u32p, u8p, u8p, u32p, u32p, u32p, u32p] + [u32p] * 22 + [u8p, u8p]),
     ("phmm_assembly_seqgraph", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u32p, u32p, u8p, u32p, u32p, C.c_uint32, u32p, u32p, u32p, u32p, u32p,
                                          u32p, u32p, u8p, u32p, u32p, u8p, u8p, u8p, u32p, u32p, u32p] + [u32p] * 17 + [u8p, u32p, u8p, u32p]),
+    ("phmm_assembly_best_paths", C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, u8p, u32p, u8p, u32p, u32p, u32p, u8p,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u8p, u32p, u32p] + [u32p] * 8 +
+                                           [f64p, u8p, u32p, u32p, u32p, u32p, u8p, u8p, u8p]),
     ("phmm_trim_regions", C.c_int, [C.c_void_p, C.c_uint32, u32p, u8p, u64p, u64p, u64p, u64p, u64p, u32p, u32p, u8p, u32p, u32p, u32p,
                                     u64p, u64p, u8p, C.c_uint32, u32p, C.POINTER(C.c_int32), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
                                     u64p, u64p, C.POINTER(C.c_int32), u32p, u32p, u32p, u8p, u32p, u32p, u32p, u32p, u8p,

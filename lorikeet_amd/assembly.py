@@ -3,7 +3,8 @@ the verdicts that reject a k before a vertex exists, the sizes of the non-unique
 whether its k-mer is non-unique, threaded, a threading start, the first of its bytes, with its dense id; and the raw
 read-threading graph itself (phmm_assembly_graph): vertices, edges, weights, the reference path, per (k, region); and what the
 assembler prunes from it before it looks for paths (phmm_assembly_prune), recovers at its dangling ends (phmm_assembly_recover)
-and zips into the sequence graph (phmm_assembly_seqgraph)."""
+and zips into the sequence graph (phmm_assembly_seqgraph), and the k best haplotype paths of such graphs
+(phmm_assembly_best_paths)."""
 import ctypes as C
 
 import numpy as np
@@ -417,4 +418,85 @@ def sequence_graph(engine, regions, graph, applied=None, connected=None, read_fi
     for name, dt in SEQ_EDGE:
         o[name] = np.zeros(0, dt) if o[name] is None else o[name][:n_edge]
     o["seq_bases"] = np.zeros(0, np.uint8) if o["seq_bases"] is None else o["seq_bases"][:n_bases]
+    return o
+
+
+PATHS_GRAPH = ("paths_status", "n_paths", "n_popped", "n_cycle_edges_removed", "n_cycle_vertices_removed")
+PATHS_OFFSETS = ("path_off", "path_edge_off", "hap_base_off")
+PATHS_PATH = (("path_score", np.float64), ("path_is_ref", np.uint8), ("path_n_edges", np.uint32))
+PATHS_OUTPUTS = (PATHS_GRAPH + PATHS_OFFSETS + tuple(n for n, _ in PATHS_PATH) +
+                 ("hap_off", "path_first_equal", "path_edges", "hap_bases", "edge_removed", "vertex_removed"))
+
+
+def best_paths(engine, seq, max_paths=128, max_nodes_per_graph=1 << 16, roles=None, regions=None, capacity=None, fill=None, omit=()):
+    """The k best haplotype paths of many sequence graphs (phmm_assembly_best_paths): the cycle removal of the reference's
+    KBestHaplotypeFinder as written, its best-first search, every path's bases and, with `regions`, the duplicate marks.  seq:
+    the dict sequence_graph returns (seq_vertex_off, seq_edge_off, seq_base_off, seq_vertex_base_off, the seq_edge arrays,
+    seq_bases, and seq_status, seq_ref_source, seq_ref_sink where present); roles: a byte per vertex (bit 0 a source, bit 1 a
+    sink) in place of seq_ref_source / seq_ref_sink, or None; regions: None, or a dict with region_ref_off and ref_bases
+    (pack()'s will do) and optionally n_k -- the graphs are then n_k x n_regions, k-major -- or a list of (reference, reads);
+    capacity: (paths, path edges, bytes), None asks the library first (a call with capacities 0, which runs the whole search: pass
+    the `required` of an earlier call over the same graphs, or any upper bound, to search once); fill: a byte the output
+    arrays hold before the call, omit: names of arrays to pass as NULL (tests).  Returns a dict of numpy arrays: paths_status,
+    n_paths, n_popped, n_cycle_edges_removed, n_cycle_vertices_removed [n_graphs]; path_off, path_edge_off, hap_base_off
+    [n_graphs + 1]; path_score, path_is_ref, path_n_edges, path_first_equal (with regions) [paths]; hap_off [paths + 1];
+    path_edges, hap_bases; edge_removed [edges], vertex_removed [vertices]; required.  Raises PhmmError; after
+    PHMM_ERR_EVENT_CAPACITY its `required` attribute holds the sizes."""
+    u32 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint32).reshape(-1)  # noqa: E731
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8).reshape(-1)  # noqa: E731
+    s32 = {name: u32(seq.get(name)) for name in ("seq_vertex_off", "seq_edge_off", "seq_base_off", "seq_vertex_base_off", "seq_edge_src", "seq_edge_dst",
+                                                 "seq_edge_multiplicity", "seq_status", "seq_ref_source", "seq_ref_sink")}
+    edge_is_ref, seq_bases, roles = u8(seq.get("seq_edge_is_ref")), u8(seq.get("seq_bases")), u8(roles)
+    n_graphs = 0 if s32["seq_vertex_off"] is None else max(len(s32["seq_vertex_off"]), 1) - 1
+    n_v = int(s32["seq_vertex_off"][-1]) if n_graphs else 0
+    n_e = int(s32["seq_edge_off"][-1]) if n_graphs and s32["seq_edge_off"] is not None and len(s32["seq_edge_off"]) else 0
+    n_regions = n_k = 0
+    region_ref_off = ref_bases = None
+    if regions is not None:
+        a = regions if isinstance(regions, dict) else pack(regions)
+        region_ref_off, ref_bases = u32(a.get("region_ref_off")), u8(a.get("ref_bases"))
+        n_regions = 0 if region_ref_off is None else max(len(region_ref_off), 1) - 1
+        n_k = int(a["n_k"]) if "n_k" in a else (n_graphs // n_regions if n_regions else 0)
+    new = lambda n, dt: np.zeros(n, dt) if fill is None else np.frombuffer(bytes([fill]) * (n * np.dtype(dt).itemsize), dt).copy()  # noqa: E731
+    types = {np.dtype(np.uint8): _lib.u8p, np.dtype(np.uint32): _lib.u32p, np.dtype(np.float64): _lib.f64p}
+
+    def call(cap):
+        cap = np.ascontiguousarray(cap, np.uint32)
+        o = dict(required=new(3, np.uint32))
+        o.update({name: new(n_graphs, np.uint32) for name in PATHS_GRAPH})
+        o.update({name: new(n_graphs + 1, np.uint32) for name in PATHS_OFFSETS})
+        o.update({name: new(int(cap[0]), dt) if cap[0] else None for name, dt in PATHS_PATH})
+        o.update(hap_off=new(int(cap[0]) + 1, np.uint32), path_first_equal=new(int(cap[0]), np.uint32) if regions is not None and cap[0] else None)
+        o.update(path_edges=new(int(cap[1]), np.uint32) if cap[1] else None, hap_bases=new(int(cap[2]), np.uint8) if cap[2] else None)
+        o.update(edge_removed=new(n_e, np.uint8), vertex_removed=new(n_v, np.uint8))
+        for name in omit:
+            o[name] = None
+        ptr = lambda name: None if o[name] is None else _p(o[name], types[o[name].dtype])  # noqa: E731
+        code = engine.lib.phmm_assembly_best_paths(
+            engine._h, n_graphs, *[_p(s32[name], _lib.u32p) for name in ("seq_vertex_off", "seq_edge_off", "seq_base_off", "seq_vertex_base_off", "seq_edge_src", "seq_edge_dst")],
+            _p(edge_is_ref, _lib.u8p), _p(s32["seq_edge_multiplicity"], _lib.u32p), _p(seq_bases, _lib.u8p), _p(s32["seq_status"], _lib.u32p),
+            _p(s32["seq_ref_source"], _lib.u32p), _p(s32["seq_ref_sink"], _lib.u32p), _p(roles, _lib.u8p), max_paths, max_nodes_per_graph, n_regions, n_k,
+            None if "region_ref_off" in omit else _p(region_ref_off, _lib.u32p), None if "ref_bases" in omit else _p(ref_bases, _lib.u8p),
+            None if "capacity" in omit else _p(cap, _lib.u32p), ptr("required"), *[ptr(name) for name in PATHS_OUTPUTS])
+        return code, o
+
+    if capacity is None:
+        code, o = call((0, 0, 0))
+        if code == _lib.PHMM_ERR_EVENT_CAPACITY:
+            code, o = call(o["required"])
+    else:
+        code, o = call(capacity)
+    if code != _lib.PHMM_OK:
+        err = PhmmError(code, engine.last_error())
+        err.required = None if o["required"] is None else o["required"].copy()
+        err.outputs = {name: v for name, v in o.items() if v is not None and name != "required"}
+        raise err
+    n_path, n_edge, n_bases = (int(x) for x in o["required"])
+    for name, dt in PATHS_PATH:
+        o[name] = np.zeros(0, dt) if o[name] is None else o[name][:n_path]
+    if regions is not None:
+        o["path_first_equal"] = np.zeros(0, np.uint32) if o["path_first_equal"] is None else o["path_first_equal"][:n_path]
+    o["hap_off"] = np.zeros(1, np.uint32) if o["hap_off"] is None else o["hap_off"][:n_path + 1]
+    o["path_edges"] = np.zeros(0, np.uint32) if o["path_edges"] is None else o["path_edges"][:n_edge]
+    o["hap_bases"] = np.zeros(0, np.uint8) if o["hap_bases"] is None else o["hap_bases"][:n_bases]
     return o

@@ -244,8 +244,8 @@ void phmm_destroy(phmm_handle *h) {
         if (h->arenas[i].host) (void)hipHostFree(h->arenas[i].host);
         if (h->arenas[i].rescue) (void)hipFree(h->arenas[i].rescue);
     }
-    for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging, &h->events_staging, &h->activity_staging, &h->finalize_staging, &h->phase_staging, &h->asm_staging, &h->graph_staging, &h->prune_staging, &h->recover_staging, &h->seqgraph_staging, &h->trim_staging, &h->regions_staging, &h->regions_out_staging, &h->regions_reads_staging}) b->release();
-    for (DeviceScratch *b : {&h->events_scratch, &h->activity_scratch, &h->finalize_scratch, &h->phase_scratch, &h->asm_scratch, &h->prune_scratch, &h->recover_scratch, &h->seqgraph_scratch}) b->release();
+    for (StagingBuffer *b : {&h->swork.staging, &h->gwork.staging, &h->af_staging, &h->annotate_staging, &h->assign_staging, &h->events_staging, &h->activity_staging, &h->finalize_staging, &h->phase_staging, &h->asm_staging, &h->graph_staging, &h->prune_staging, &h->recover_staging, &h->seqgraph_staging, &h->paths_staging, &h->trim_staging, &h->regions_staging, &h->regions_out_staging, &h->regions_reads_staging}) b->release();
+    for (DeviceScratch *b : {&h->events_scratch, &h->activity_scratch, &h->finalize_scratch, &h->phase_scratch, &h->asm_scratch, &h->prune_scratch, &h->recover_scratch, &h->seqgraph_scratch, &h->paths_scratch, &h->paths_table}) b->release();
     if (h->swork.slab) (void)hipFree(h->swork.slab);
     if (h->swork.ws) (void)hipFree(h->swork.ws);
     if (h->swork.ext) (void)hipFree(h->swork.ext);

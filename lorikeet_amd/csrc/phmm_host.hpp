@@ -179,6 +179,7 @@ struct phmm_handle {
     StagingBuffer prune_staging;  // phmm_assembly_prune (phmm_prune.cpp)
     StagingBuffer recover_staging;  // phmm_assembly_recover (phmm_recover.cpp)
     StagingBuffer seqgraph_staging;  // phmm_assembly_seqgraph (phmm_seqgraph.cpp)
+    StagingBuffer paths_staging;  // phmm_assembly_best_paths (phmm_paths.cpp)
     // phmm_assembly_regions (phmm_regions.cpp): per state and read, per region, per membership -- each sized once its count is known
     StagingBuffer regions_staging, regions_out_staging, regions_reads_staging;
     // the device-only workspaces of the same entry points
@@ -190,6 +191,10 @@ struct phmm_handle {
     DeviceScratch prune_scratch;     // phmm_assembly_prune: degrees, marks and chain pointers, 20 bytes per vertex and 5 per edge
     DeviceScratch recover_scratch;   // phmm_assembly_recover: the working graphs (41 bytes per vertex slot, 17 per edge slot) and the aligner's slabs
     DeviceScratch seqgraph_scratch;  // phmm_assembly_seqgraph: the graphs' state, 84 bytes per vertex, 5 per edge and 16 per sort slot
+    DeviceScratch paths_scratch;     // phmm_assembly_best_paths: the graphs' state, 20 bytes per vertex, 4 per edge and 45 per search-tree node
+    DeviceScratch paths_table;       // ... and L[n] = log10((double)n), grown to the largest per-vertex total met (phmm_paths.cpp)
+    std::vector<double> paths_log10;  // the table on the host, built with the C library's log10
+    size_t paths_log10_on_device = 0;
     uint64_t stat_staged_bytes = 0;   // payload bytes copied into pinned staging by this handle (phmm_get_stat)
     uint64_t stat_rescue_passes = 0;  // how many batches needed the exact pass (phmm_get_stat)
     struct Combiner *comb = nullptr;  // phmm_submit / phmm_wait state, created by the first phmm_submit

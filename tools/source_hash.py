@@ -26,6 +26,7 @@ KERNEL_SOURCES = {  # what each kernel family is compiled from (lorikeet_amd/csr
     "prune": ("phmm_prune_internal.hpp", "phmm_prune_kernels.hip"),
     "recover": ("phmm_recover_internal.hpp", "phmm_recover_kernels.hip"),
     "seqgraph": ("phmm_seqgraph_internal.hpp", "phmm_seqgraph_kernels.hip"),
+    "paths": ("phmm_paths_internal.hpp", "phmm_paths_kernels.hip"),
     "trim": ("phmm_trim_internal.hpp", "phmm_trim_kernels.hip", "phmm_events_internal.hpp", "phmm_events_kernels.hip",
              "phmm_cigar_internal.hpp", "phmm_cigar_device.hpp"),
     "regions": ("phmm_regions_internal.hpp", "phmm_regions_kernels.hip"),
